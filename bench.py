@@ -26,6 +26,7 @@ Objects on that line:
                   c5_fp32 / c5_fp16 (configs[4]).
 """
 import argparse
+import copy
 import json
 import os
 import socket
@@ -236,7 +237,7 @@ class Run:
 
 	PRIME_S = 0.6   # see timed()
 
-	def timed(self, step, steps, warmup, prime=True):
+	def timed(self, step, steps, warmup, prime=True, before_last=None):
 		"""_timed() with the backward passes on this thread, as find_amd.trainer.Trainer runs its loops (train_utils.backward_on_this_thread:
 		autograd's worker thread costs the host 0.5 ms per step and made the eager loop host-bound; FIND_AUTOGRAD_THREADS=1 for torch's default)."""
 		from find_amd.train_utils import backward_on_this_thread
@@ -248,14 +249,15 @@ class Run:
 			own = self.__dict__.setdefault('_own_stream', torch.cuda.Stream(device=self.dev))
 			torch.cuda.synchronize()
 		with backward_on_this_thread(), (torch.cuda.stream(own) if own is not None else contextlib.nullcontext()):
-			return self._timed(step, steps, warmup, prime)
+			return self._timed(step, steps, warmup, prime, before_last)
 
-	def _timed(self, step, steps, warmup, prime=True):
+	def _timed(self, step, steps, warmup, prime=True, before_last=None):
 		"""W untimed warm-up steps, then exactly K timed steps between barrier + synchronize on both sides (the driver's contract).  Before
 		the warm-up the workload is PRIMED -- untimed steps for at least PRIME_S seconds, until the step time has settled -- so that first-use
 		costs of a fresh process (allocator growth, queue probing, module loads) are behind it whatever W is.  What is timed is unchanged:
 		K steps of the steady state.  `--no-prime` switches it off.  (what looked like a cold-start effect when this was added was
-		a reference cycle in the product, found by the repeats and fixed.)"""
+		a reference cycle in the product, found by the repeats and fixed.)  `before_last()` runs before the last timed step, with the clock
+		stopped around it and the device idle on both sides."""
 		if prime and Run.PRIME_S > 0:
 			# batches of eight steps until at least PRIME_S seconds have gone by AND two consecutive batches agree within 5 % (at most
 			# 8 x PRIME_S: the first process on a fresh box also pays first-use costs -- allocator growth, queue probing, module loads --
@@ -282,12 +284,19 @@ class Run:
 		self.barrier()
 		torch.cuda.synchronize()
 		t0 = time.perf_counter()
-		for _ in range(steps):
+		paused = 0.0
+		for i in range(steps):
+			if before_last is not None and i == steps - 1:
+				torch.cuda.synchronize()
+				tp = time.perf_counter()
+				before_last()
+				torch.cuda.synchronize()
+				paused += time.perf_counter() - tp
 			step()
 		torch.cuda.synchronize()
 		self.barrier()
 		torch.cuda.synchronize()
-		elapsed = time.perf_counter() - t0
+		elapsed = time.perf_counter() - t0 - paused
 		if self.world > 1:
 			t = torch.tensor([elapsed], device=self.dev, dtype=torch.float64)
 			torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
@@ -323,6 +332,32 @@ def line(value, ms, run, steps, warmup, config, **extra):
 	return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, su):
+	"""--dump-outputs: what the headline step handed its caller in its last timed step, as <path>/<name>.npy (float32): the loss and its
+	terms (loss.npy, loss_<term>.npy), every trainable parameter after the optimiser step (param.<name>.npy) and the gradient it was
+	stepped with (grad.<name>.npy).  Whole tensors: about 7 MB at the headline's size."""
+	import numpy as np
+	torch.cuda.synchronize()
+	arrays = dict(su['state']['last'])
+	for name, p in su['mwl'].named_parameters():
+		if not p.requires_grad:   # the template: an input of the step
+			continue
+		arrays[f'param.{name}'] = p.detach()
+		if p.grad is not None:
+			arrays[f'grad.{name}'] = p.grad
+	arrays = {k: v.float().cpu().numpy() for k, v in arrays.items()}
+	total = sum(a.nbytes for a in arrays.values())
+	if total > DUMP_LIMIT_BYTES:
+		raise SystemExit(f'bench.py --dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit')
+	os.makedirs(path, exist_ok=True)
+	for k, a in arrays.items():
+		np.save(os.path.join(path, k + '.npy'), a)
+	note(f'dumped {len(arrays)} arrays ({total / 1e6:.1f} MB) to {path}')
+
+
 # ------------------------------------------------------------------------------------------------ train_3d.yaml
 def make_mwl(dev, n_items, opts, n_verts=None, labels=None, size=None, val_size=2):
 	from find_amd import synthetic
@@ -352,13 +387,15 @@ def fill_latents(m, n_feet, seed, dev):
 			t.copy_(lat[k][:t.shape[0]])
 
 
-def train3d_setup(run, n_items, batch_size, stage='net', labels=False, seed=0, dp=True, capturable=False, frozen=False):
+def train3d_setup(run, n_items, batch_size, stage='net', labels=False, seed=0, dp=True, capturable=False, frozen=False, dump=False):
 	"""One step of the train_3d.yaml experiment as src/train/trainer.py runs it.  stage 'net' (train.py:211-215, trainer.py:97-123): losses
 	chamf + smooth + texture, optim_network = Adam(main_params); stage 'reg' (train.py:197-209): chamf only, optim_reg = SGD(reg_params,
 	momentum 0.9); stage 'latent' (train.py:217-224 -> Trainer.val_epoch, trainer.py:150-163): the same three losses with is_train=False on
 	the validation scans, their `*_val` rows, optim_latent = Adam(latent_params) -- `frozen` additionally takes requires_grad off the
 	network's weights (nothing steps them in this stage; the reference leaves them trainable and computes their gradients for nothing).
-	batch_size < n_items walks the items round-robin like the DataLoader (batch_size_train / _val default to 1, opts.py:40-41)."""
+	batch_size < n_items walks the items round-robin like the DataLoader (batch_size_train / _val default to 1, opts.py:40-41).
+	dump (--dump-outputs): step() keeps the loss terms of its last call (detached) in su['state']['last'], and su['rewind']() puts the weights,
+	latent tables, their gradients, optimiser state and random generators back where this function left them."""
 	from find_amd import distributed as fdist
 	from find_amd import optim, synthetic
 	from find_amd.opts import Opts
@@ -414,20 +451,36 @@ def train3d_setup(run, n_items, batch_size, stage='net', labels=False, seed=0, d
 	if val:
 		flags['is_train'] = False
 	vectors = m.latent_vectors_val if val else m.latent_vectors_train
-	state = dict(i=0)
+	state = dict(i=0, last=None)
 
 	def step():
 		opt.zero_grad(set_to_none=True)
 		b = dict(batches[state['i'] % len(batches)])
 		state['i'] += 1
 		b.update(sample_latent_vectors(b, vectors))
-		loss, _ = mwl(b, 0, opts, **flags)
+		loss, losses = mwl(b, 0, opts, **flags)
 		train_backward(loss)
 		if bucket is not None:
 			bucket.allreduce_(async_op=True)   # the latent tables' part (the weights' part left inside the backward: GradBucket.arm_early);
 			bucket.wait()                      # the optimiser needs both: the wait follows at once (stream-side dependency, the host does not block)
 		opt.step()
+		if dump:   # detached: the step's autograd graph must not outlive it
+			state['last'] = dict(loss=loss.detach(), **{k: v.detach() for k, v in losses.items()})
 		return loss
+
+	rewind = None
+	if dump:
+		init = dict(model={k: v.detach().clone() for k, v in mwl.state_dict().items()}, opt=copy.deepcopy(opt.state_dict()),
+					rng=torch.get_rng_state(), rng_dev=torch.cuda.get_rng_state(dev))
+
+		def rewind():
+			mwl.load_state_dict(init['model'])
+			for p in mwl.parameters():   # (the optimiser's zero_grad leaves the gradients of what it does not step -- reg -- to accumulate)
+				p.grad = None
+			opt.load_state_dict(copy.deepcopy(init['opt']))
+			torch.set_rng_state(init['rng'])
+			torch.cuda.set_rng_state(init['rng_dev'], dev)
+			state.update(i=0, last=None)
 
 	def collective(iters=20):
 		"""What the N > 1 line says about the exchange step (every rank calls this): backend, the world size the process group reports, the
@@ -454,7 +507,7 @@ def train3d_setup(run, n_items, batch_size, stage='net', labels=False, seed=0, d
 					allreduce_us_per_step=e0.elapsed_time(e1) / iters * 1e3, ranks_devices=[f"{r['rank']}:{r['device']}" + (f"@{r['pci_bus']}" if r['pci_bus'] is not None else '') for r in ranks],
 					distinct_devices=len({(r['device'], r['pci_bus'], r['uuid']) for r in ranks}))
 
-	return dict(mwl=mwl, step=step, gt=(gv, gf, gc), opts=opts, opt=opt, batches=batches, flags=flags, collective=collective)
+	return dict(mwl=mwl, step=step, gt=(gv, gf, gc), opts=opts, opt=opt, batches=batches, flags=flags, collective=collective, state=state, rewind=rewind)
 
 
 def train3d_executed_flops(n_feet, n_verts=None, n_tex=1000, stage='net', frozen=False, lazy_col=None):
@@ -1100,7 +1153,15 @@ def main():
 	ap.add_argument('--c4', action='store_true', help='per-rank share of BASELINE configs[3]: 16 feet x 4 views @512^2, silhouette + pixel + Chamfer losses')
 	ap.add_argument('--dp-overhead', action='store_true', help='diagnostic: run the C2 step on ONE GPU through the data-parallel code path (one-rank RCCL group, gradient bucket + all-reduce)')
 	ap.add_argument('--subpaths', action='store_true', help='instead of the headline line: one JSON line per render / Chamfer / smoothness sub-path (SURVEY 8d), CPU oracle timed beside each')
+	ap.add_argument('--dump-outputs', metavar='DIR', help='headline: after the timed steps, write what the last timed step returned (loss terms, the '
+					'stepped parameters, their gradients) as DIR/<name>.npy.  That step starts from the state setup left (weights, gradients, '
+					'optimiser, random generators; restored with the clock stopped), so every run computes it from the same inputs, and its arrays '
+					'differ from another run\'s only by the rounding of the float atomics in the backward of the surface sampling and the Chamfer term')
 	args = ap.parse_args()
+	if args.steps < 1 or args.warmup < 0:
+		ap.error('--steps must be at least 1 and --warmup at least 0')
+	if args.dump_outputs and (args.c2 or args.c3 or args.c4 or args.c5 or args.dp_overhead or args.train3d_b1 or args.subpaths):
+		ap.error('--dump-outputs writes the headline step\'s outputs; it does not combine with the other configurations')
 
 	if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
 		raise SystemExit(spawn_ranks(sys.argv[1:], args.gpus))
@@ -1140,12 +1201,17 @@ def main():
 
 	# ---- headline: train_3d.yaml network-stage step, 16 feet per GPU
 	note('headline')
-	su = train3d_setup(run, N_FEET, N_FEET, stage='net', labels=False, seed=run.rank)
+	su = train3d_setup(run, N_FEET, N_FEET, stage='net', labels=False, seed=run.rank, dump=bool(args.dump_outputs))
 	# The headline's K-step timing is taken `--repeats` times (default 5; each: W warm-up steps, exactly K steps between barrier +
 	# synchronize, the maximum over ranks) and the MEDIAN is reported, every repetition listed beside it (`ms_per_step_repeats`): a step whose
 	# host work is most of its GPU time is sensitive to whatever else the host does, and a run that drifts shows in the list.
-	ms_all = [run.timed(su['step'], args.steps, args.warmup, prime=(i == 0)) for i in range(max(1, args.repeats))]
+	# --dump-outputs: the last timed step of the last repetition starts from the state setup left (su['rewind']): the float atomics of the
+	# sampling and Chamfer backward round differently in every run, and Adam would carry that into every later step's inputs.
+	n_rep = max(1, args.repeats)
+	ms_all = [run.timed(su['step'], args.steps, args.warmup, prime=(i == 0), before_last=su['rewind'] if i == n_rep - 1 else None) for i in range(n_rep)]
 	ms = sorted(ms_all)[(len(ms_all) - 1) // 2]
+	if args.dump_outputs and run.rank == 0:
+		dump_outputs(args.dump_outputs, su)
 	coll = su['collective']() if run.world > 1 else None
 	full = {}   # everything that does not fit the line: RECORDS_FILE
 	if run.rank == 0:

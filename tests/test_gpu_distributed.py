@@ -246,6 +246,7 @@ def test_one_rank_rccl_step_keeps_the_stream_layout_and_the_step_time():
 	import sys
 	root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 	env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0', MASTER_ADDR='127.0.0.1')
+	hw_queues = int(os.environ.get('GPU_MAX_HW_QUEUES', '4'))   # HIP's hardware queues per process: four unless the host sets fewer
 	def measure():
 		res = {}
 		for mode in ('plain', 'dp'):
@@ -262,7 +263,10 @@ def test_one_rank_rccl_step_keeps_the_stream_layout_and_the_step_time():
 	for attempt in range(3):
 		res = measure()
 		for mode, (g, _) in res.items():
-			assert g[1] != g[0] and g[2] != g[0] and g[3] != g[0], f'{mode}: a side stream shares the hardware queue of the caller: {g}'
+			if hw_queues >= 4:
+				assert g[1] != g[0] and g[2] != g[0] and g[3] != g[0], f'{mode}: a side stream shares the hardware queue of the caller: {g}'
+			else:   # too few queues for that layout (tests/test_gpu_mlp.py HW_QUEUES): the probe still tells them all apart
+				assert len(set(g)) == hw_queues, f'{mode}: {g} over {hw_queues} hardware queues'
 		ratio = res['dp'][1] / res['plain'][1]
 		print(f"one-rank RCCL step {res['dp'][1]:.3f} ms against {res['plain'][1]:.3f} ms plain: x{ratio:.3f}; queue groups {res['dp'][0]} / {res['plain'][0]}")
 		if ratio < 1.08:

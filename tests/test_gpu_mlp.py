@@ -1,5 +1,7 @@
 """GPU parity: HIP MLP / registration (through the C-ABI) vs the golden vectors captured from the reference and
 vs the torch-CPU oracle.  Tolerance: the north_star's 1e-4 (fp32); observed errors are ~1e-6."""
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -7,6 +9,9 @@ import torch
 from oracle import mlp_ref
 
 pytestmark = pytest.mark.gpu
+# HIP's hardware queues per device and process: four unless the host sets fewer.  The side-stream layout (Q, T1, T2 each on a queue of
+# its own beside the caller's) needs four; with fewer the probe finds none and the context keeps its streams as created.
+HW_QUEUES = int(os.environ.get('GPU_MAX_HW_QUEUES', '4'))
 TOL = 1e-4
 
 
@@ -654,8 +659,11 @@ def test_side_streams_are_bound_to_queues_beside_the_callers():
 		_lib.check(L.find_ctx_stream_groups(h, _lib.current_stream(torch.device('cuda')), ctypes.cast(g, ctypes.c_void_p)), 'find_ctx_stream_groups')
 		caller, q, t1, t2, r = list(g)
 		assert caller == 0
-		assert len({caller, q, t1, t2}) == 4, list(g)
-		assert r == t2, list(g)
+		if HW_QUEUES >= 4:
+			assert len({caller, q, t1, t2}) == 4, list(g)
+			assert r == t2, list(g)
+		else:   # the probe tells the process's queues apart: as many groups as queues
+			assert len(set(g)) == HW_QUEUES, list(g)
 	finally:
 		_lib.check(L.find_ctx_destroy(h), 'find_ctx_destroy')
 	del clutter
@@ -675,21 +683,26 @@ def test_stream_beside_picks_a_stream_on_the_asked_hardware_queue():
 	cands = [torch.cuda.Stream(device=dev) for _ in range(12)]
 	arr = (ctypes.c_void_p * len(cands))(*[c.cuda_stream for c in cands])
 	idx = ctypes.c_int32(-7)
+	g2 = (ctypes.c_int32 * 5)()
+	_lib.check(L.find_ctx_stream_groups(h, ctypes.c_void_p(main.cuda_stream), ctypes.cast(g2, ctypes.c_void_p)), 'find_ctx_stream_groups')
 	for role in (0, 1, 2):
 		_lib.check(L.find_ctx_stream_beside(h, ctypes.c_void_p(main.cuda_stream), arr, len(cands), role, ctypes.byref(idx)), 'find_ctx_stream_beside')
-		assert 0 <= idx.value < len(cands), (role, idx.value)   # (twelve streams over four hardware queues: every queue is met)
+		if HW_QUEUES < 4 and g2[1 + role] == g2[0]:   # this side stream shares the caller's queue: no candidate on it runs beside the caller
+			assert idx.value == -1, (role, idx.value, list(g2))
+			continue
+		assert 0 <= idx.value < len(cands), (role, idx.value)   # (twelve streams over the hardware queues: every queue is met)
 		g = (ctypes.c_int32 * 5)()
 		_lib.check(L.find_ctx_stream_groups(h, ctypes.c_void_p(cands[idx.value].cuda_stream), ctypes.cast(g, ctypes.c_void_p)), 'find_ctx_stream_groups')
 		assert g[1 + role] == g[0], (role, list(g))                 # the candidate (group 0 here) shares side stream `role`'s queue
-		g2 = (ctypes.c_int32 * 5)()
-		_lib.check(L.find_ctx_stream_groups(h, ctypes.c_void_p(main.cuda_stream), ctypes.cast(g2, ctypes.c_void_p)), 'find_ctx_stream_groups')
 		assert g2[1 + role] != g2[0]                                 # ... which is not the caller's
 	assert L.find_ctx_stream_beside(h, ctypes.c_void_p(main.cuda_stream), arr, len(cands), 9, ctypes.byref(idx)) != 0
 	assert L.find_ctx_stream_beside(h, ctypes.c_void_p(main.cuda_stream), None, len(cands), 0, ctypes.byref(idx)) != 0
 	side = _second_stream(dev)
 	g = (ctypes.c_int32 * 5)()
 	_lib.check(L.find_ctx_stream_groups(h, ctypes.c_void_p(side.cuda_stream), ctypes.cast(g, ctypes.c_void_p)), 'find_ctx_stream_groups')
-	assert g[1] == g[0], list(g)   # Q's queue
+	# Q's queue; with fewer queues, where Q may share the caller's, the queue of the first of T1, T2, R, Q that does not
+	first = 0 if HW_QUEUES >= 4 else next(k for k in (1, 2, 3, 0) if g2[1 + k] != g2[0])
+	assert g[1 + first] == g[0], (first, list(g), list(g2))
 	torch.cuda.synchronize()
 
 
