@@ -3,7 +3,7 @@ finishes in a second or two and reach the full configurations by composition; he
 
   (a) the headline step -- bench.py's own `train3d_setup`: 16 feet x 6890-vertex template, 10 002-vertex GT scans, 5000 / 1000 surface
       samples, chamf + smooth + texture (cfgs/train_3d.yaml:17-27; src/model/model.py:1001-1163) -- losses and gradients of all four
-      latent tables and nine weight tensors against the oracle's composition of the same step with the sampler's draws replayed;
+      latent tables and all 26 weight / bias tensors against the oracle's composition of the same step with the sampler's draws replayed;
   (b) the 6890-vertex template @256^2 (C3 geometry), one foot x one view: mask, Phong image, nearest-face map, and the gradients of a
       silhouette and of an image loss against autograd through the oracle's fragments (src/model/renderer.py:247-311);
   (c) one image @512^2 of the C4 geometry: the same forward checks and the silhouette gradient;
@@ -74,7 +74,9 @@ def test_headline_step_batch16_full_size_matches_oracle():
 		worst[k] = (got - want).abs().max().item() / s
 		assert worst[k] < TOL, (k, worst[k])
 	params = dict(m.named_parameters())
-	for k in WEIGHTS:
+	trainable = [k for k, v in sd.items() if v.requires_grad]
+	assert len(trainable) == 26 and set(WEIGHTS) <= set(trainable)
+	for k in trainable:   # every weight / bias tensor (WEIGHTS: the ten this test checked before)
 		got, want = params[k].grad.cpu(), sd[k].grad
 		s = max(1e-3, want.abs().max().item())
 		worst[k] = (got - want).abs().max().item() / s
