@@ -6,7 +6,7 @@ fault reproducers, superseded kernels, timers, wrong-result ablation bits).  Onl
 __graft_entry__ run the product."""
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_float, c_int, c_int32, c_int64, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_float, c_int, c_int16, c_int32, c_int64, c_void_p
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 DIAG = os.environ.get('FIND_DIAG', '0') not in ('', '0')
@@ -42,7 +42,7 @@ class MlpGrads(Structure):
 class RenderParams(Structure):
 	_fields_ = [
 		('image_h', c_int32), ('image_w', c_int32), ('fov_deg', c_float), ('znear', c_float), ('zfar', c_float),
-		('sil_blur_radius', c_float), ('sil_sigma', c_float), ('sil_faces_per_pixel', c_int32),
+		('sil_blur_radius', c_float), ('sil_sigma', c_float), ('sil_faces_per_pixel', c_int16), ('clip_faces', c_int16),
 		('rgb_sigma', c_float), ('rgb_gamma', c_float), ('background', c_float * 3), ('light_pos', c_float * 3),
 		('ambient', c_float), ('diffuse', c_float), ('specular', c_float), ('shininess', c_float), ('z_clip', c_float),
 	]

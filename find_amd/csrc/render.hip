@@ -26,6 +26,9 @@
 //      in registers: no per-fragment atomics); projection backward is a deterministic sum over views.
 // Every kernel evaluates a (pixel, face) pair with the SAME rounding (eval_frag is compiled without fp contraction, its fused
 // multiply-adds are written out): the depth a candidate had in the forward is the depth the fix-up and the backward recompute.
+// Split mode (find_render_params.clip_faces = 1): faces that straddle the z-clip plane are clipped into one or two
+// triangles by face_setup_kernel<true>; every per-face array then holds 2 F SLOTS per image, steps 3-5 run over slots unchanged,
+// clip_frag_kernel converts the nearest fragment back to the original face, clip_chain_kernel takes the clipped slots' gradients back.
 // Conventions: SURVEY.md Appendix A.2-A.4 (row-vector transforms, NDC +x left / +y up, image = mesh*n_views + view).
 #include <type_traits>
 
@@ -88,6 +91,12 @@ struct Ws {
 	uint32_t* pool;   // list entries: slab << 24 | face
 	int32_t* order;   // (n_img * tiles) ids of the tiles that have a list, the longest lists first
 	Fix* fix;         // (n_img * H * W) fix-up queue
+	// clip_faces = 1 only (null otherwise): every per-face array above holds n_slots = 2 F slots per image (slot f: face f or its first /
+	// only clipped triangle, slot F + f: the second triangle of a split quad), and
+	float4* crec;     // (n_img, 2 F) clip record of a slot: [w0 w1 w2 | packed]: sub-vertex k = (1 - w_k) v_a + w_k v_b (clip_slot)
+	float* d_sub;     // (n_img, 2 F, 12) backward: gradients of a CLIPPED slot's three vertices (x, y, z) and of its w0..w2 (clip_chain_kernel)
+	int32_t* p2s;     // (n_img, H, W) slot of the nearest inside fragment (p2f holds the original face)  [RGB backward]
+	int64_t n_slots;
 	int64_t pool_cap, n_tiles, raster_wgs;
 	int64_t bytes;
 };
@@ -96,18 +105,20 @@ static void carve(const find_render_params* rp, int64_t n_meshes, int64_t n_view
 	Carver c(ws);
 	const int64_t n_img = n_meshes * n_views;
 	const int64_t px = n_img * rp->image_h * rp->image_w;
+	const int64_t NS = rp->clip_faces ? 2 * F : F;   // face slots per image
+	o->n_slots = NS;
 	o->flags = c.take<int32_t>(64);
 	o->qn = c.take<int32_t>(64);
 	// per image: entries handed out of its part of the pool -- one counter per 128-byte line (atomics on one line are served one after
 	// the other, ~50 ns each: 64 counters packed into two lines were the slowest thing in the binning kernel, 260 us)
 	o->cursor = c.take<int32_t>(n_img * CURSOR_STRIDE);
 	o->vproj = c.take<float>(n_img * V * 3);
-	o->frec = c.take<float4>(n_img * F * 3);
-	o->recs = reinterpret_cast<FaceRec*>(c.take<float4>(n_img * F * REC_F4));
-	o->rz = c.take<uint32_t>(n_img * cdiv(F, 64) * 4);
-	o->tb = c.take<uint32_t>(n_img * F);
-	o->tbb = c.take<uint32_t>(n_img * cdiv(F, 64));
-	o->fzmin = c.take<float>(n_img * F);
+	o->frec = c.take<float4>(n_img * NS * 3);
+	o->recs = reinterpret_cast<FaceRec*>(c.take<float4>(n_img * NS * REC_F4));
+	o->rz = c.take<uint32_t>(n_img * cdiv(NS, 64) * 4);
+	o->tb = c.take<uint32_t>(n_img * NS);
+	o->tbb = c.take<uint32_t>(n_img * cdiv(NS, 64));
+	o->fzmin = c.take<float>(n_img * NS);
 	o->zinfo = c.take<int32_t>(n_img * 8);
 	o->normals = c.take<float>(n_meshes * V * 3);
 	o->p2f = c.take<int32_t>(px);
@@ -127,10 +138,16 @@ static void carve(const find_render_params* rp, int64_t n_meshes, int64_t n_view
 	// a face of ~1 pixel with the silhouette's blur margin touches ~4.5 tiles at 256^2 and ~10 at 512^2; a tile that finds the pool
 	// full is rasterised from the face arrays directly (slower, never wrong)
 	// (every image has its own part of the pool and its own cursor: one cursor for all was the hottest address of the launch)
-	o->pool_cap = std::min<int64_t>(F * 16 + (1 << 14), ((int64_t)1 << 30) / n_img);
+	o->pool_cap = std::min<int64_t>(NS * 16 + (1 << 14), ((int64_t)1 << 30) / n_img);
 	o->pool = c.take<uint32_t>(o->pool_cap * n_img);
 	o->order = c.take<int32_t>(o->n_tiles);
 	o->fix = c.take<Fix>(px);
+	o->crec = nullptr; o->d_sub = nullptr; o->p2s = nullptr;
+	if (rp->clip_faces) {   // (behind everything else: the default mode's layout and size do not change)
+		o->crec = c.take<float4>(n_img * NS);
+		o->d_sub = c.take<float>(n_img * NS * 12);
+		o->p2s = c.take<int32_t>(px);
+	}
 	o->bytes = c.off;
 }
 
@@ -383,24 +400,85 @@ __device__ __forceinline__ void normalize3(float& x, float& y, float& z) {
 	x /= l; y /= l; z /= l;
 }
 
+// ---- z-clip, split mode (find_render_params.clip_faces = 1; PyTorch3D clip.py with cull_to_frustum = False).  A face with one vertex
+// behind the plane z = zc becomes a quad, split into two triangles; with two behind, one triangle; with three, nothing.  The vertices are
+// rotated cyclically so that the odd one out (the one behind / the one in front) is p1, p2 and p3 following it (the orientation is kept);
+// q4 lies on edge p1 p2, q5 on edge p1 p3, and the triangles are
+//   one behind:  slot f = (q4, p2, p3), slot F + f = (q4, p3, q5)   (the quad q4 p2 p3 q5 split along its diagonal q4 p3)
+//   two behind:  slot f = (p1, q4, q5)
+// A new vertex on edge (a, b), a the vertex behind the plane: w = (zc - z_a) / (z_b - z_a), z = zc, and x, y perspective-correct,
+// ((1 - w) xy_a z_a + w xy_b z_b) / zc.  Its clip record keeps, per sub-vertex k, the edge (a_k, b_k) in 2 + 2 bits and w_k; an original
+// vertex i is (i, i, 0).  The barycentrics of the original face are then sum_k b_k [(1 - w_k) e_(a_k) + w_k e_(b_k)] (clip_frag_kernel).
+constexpr uint32_t CLIP_SPLIT = 1u << 12;    // the slot holds a clipped triangle (unset: the face itself, or an empty slot)
+constexpr uint32_t CLIP_IDENT = 0u | (5u << 4) | (10u << 8);   // (0, 0) (1, 1) (2, 2)
+__device__ __forceinline__ bool clip_slot(bool second, float zc, float& x0, float& y0, float& z0, float& x1, float& y1, float& z1,
+										  float& x2, float& y2, float& z2, float4* cr) {
+	*cr = make_float4(0.f, 0.f, 0.f, __uint_as_float(CLIP_IDENT));
+	const float xs[3] = {x0, x1, x2}, ys[3] = {y0, y1, y2}, zs[3] = {z0, z1, z2};
+	const bool bh[3] = {z0 < zc, z1 < zc, z2 < zc};
+	const int nb = (int)bh[0] + (int)bh[1] + (int)bh[2];
+	if (nb == 0) return !second;   // the face itself, in slot f
+	if (nb == 3 || (nb == 2 && second)) return false;
+	// p1: the vertex that is alone on its side of the plane
+	const int p1 = nb == 1 ? (bh[0] ? 0 : (bh[1] ? 1 : 2)) : (!bh[0] ? 0 : (!bh[1] ? 1 : 2));
+	const int p2 = p1 == 2 ? 0 : p1 + 1, p3 = p2 == 2 ? 0 : p2 + 1;
+	int ea[3], eb[3];   // the sub-triangle's vertices as edges (a, b): a == b is an original vertex
+	if (nb == 1) {
+		if (!second) { ea[0] = p1; eb[0] = p2; ea[1] = eb[1] = p2; ea[2] = eb[2] = p3; }
+		else { ea[0] = p1; eb[0] = p2; ea[1] = eb[1] = p3; ea[2] = p1; eb[2] = p3; }
+	} else {
+		ea[0] = eb[0] = p1; ea[1] = p2; eb[1] = p1; ea[2] = p3; eb[2] = p1;
+	}
+	float ox[3], oy[3], oz[3], ow[3];
+	uint32_t pk = CLIP_SPLIT;
+#pragma unroll
+	for (int k = 0; k < 3; ++k) {
+		const int a = ea[k], b = eb[k];
+		pk |= (uint32_t)(a | (b << 2)) << (4 * k);
+		if (a == b) { ox[k] = xs[a]; oy[k] = ys[a]; oz[k] = zs[a]; ow[k] = 0.f; continue; }
+		const double za = zs[a], zb = zs[b];
+		const double w = ((double)zc - za) / (zb - za);
+		ox[k] = (float)(((1.0 - w) * xs[a] * za + w * xs[b] * zb) / zc);
+		oy[k] = (float)(((1.0 - w) * ys[a] * za + w * ys[b] * zb) / zc);
+		oz[k] = zc; ow[k] = (float)w;
+	}
+	x0 = ox[0]; y0 = oy[0]; z0 = oz[0]; x1 = ox[1]; y1 = oy[1]; z1 = oz[1]; x2 = ox[2]; y2 = oy[2]; z2 = oz[2];
+	*cr = make_float4(ow[0], ow[1], ow[2], __uint_as_float(pk));
+	return true;
+}
+
 // per (image, face): cull, the records (backward: 48 B; forward: the full 80 B), the tiles its blurred bbox touches, its nearest depth;
-// per run of 64 faces: their common tile bbox and depth statistics (zinfo_kernel folds those into the image's)
+// per run of 64 faces: their common tile bbox and depth statistics (zinfo_kernel folds those into the image's).
+// SPLIT (clip_faces = 1): one thread per SLOT of 2 F (slot f and F + f: the clipped triangles of face f, clip_slot), which is then handled
+// as a face of its own -- F counts faces, the arrays hold 2 F slots per image.
+template <bool SPLIT>
 __global__ void face_setup_kernel(const float* __restrict__ vproj, const int32_t* __restrict__ faces, int64_t faces_mesh_stride,
 								  int n_views, int V, int F, int H, int W, float blur_radius, float z_clip,
 								  float4* __restrict__ frec, FaceRec* __restrict__ recs, uint32_t* __restrict__ tb, uint32_t* __restrict__ tbb,
-								  float* __restrict__ fzmin, uint32_t* __restrict__ rz, int32_t* __restrict__ flags) {
+								  float* __restrict__ fzmin, uint32_t* __restrict__ rz, int32_t* __restrict__ flags, float4* __restrict__ crec) {
+	const int NS = SPLIT ? 2 * F : F;   // slots per image
 	const int img = blockIdx.y;
 	const int f = blockIdx.x * blockDim.x + threadIdx.x;
 	const int mesh = img / n_views;
-	const int32_t* fp = faces + (int64_t)mesh * faces_mesh_stride + (int64_t)min(f, F - 1) * 3;
+	const int fi = SPLIT && f >= F ? f - F : f;   // the face of slot f
+	const int32_t* fp = faces + (int64_t)mesh * faces_mesh_stride + (int64_t)min(fi, F - 1) * 3;
 	uint32_t packed = TB_EMPTY;
-	const int64_t o = (int64_t)img * F + f;
+	const int64_t o = (int64_t)img * NS + f;
 	float zmn = 0.f, zext = 0.f;
-	if (f < F && fp[0] >= 0) {
+	bool have = f < NS && fp[0] >= 0;
+	float x0 = 0.f, y0 = 0.f, z0 = 0.f, x1 = 0.f, y1 = 0.f, z1 = 0.f, x2 = 0.f, y2 = 0.f, z2 = 0.f;
+	if (have) {
 		const float* vp = vproj + (int64_t)img * V * 3;
-		const float x0 = vp[3 * fp[0]], y0 = vp[3 * fp[0] + 1], z0 = vp[3 * fp[0] + 2];
-		const float x1 = vp[3 * fp[1]], y1 = vp[3 * fp[1] + 1], z1 = vp[3 * fp[1] + 2];
-		const float x2 = vp[3 * fp[2]], y2 = vp[3 * fp[2] + 1], z2 = vp[3 * fp[2] + 2];
+		x0 = vp[3 * fp[0]]; y0 = vp[3 * fp[0] + 1]; z0 = vp[3 * fp[0] + 2];
+		x1 = vp[3 * fp[1]]; y1 = vp[3 * fp[1] + 1]; z1 = vp[3 * fp[1] + 2];
+		x2 = vp[3 * fp[2]]; y2 = vp[3 * fp[2] + 1]; z2 = vp[3 * fp[2] + 2];
+	}
+	if constexpr (SPLIT) {
+		float4 cr = make_float4(0.f, 0.f, 0.f, __uint_as_float(CLIP_IDENT));
+		if (have) have = clip_slot(f >= F, z_clip, x0, y0, z0, x1, y1, z1, x2, y2, z2, &cr);
+		if (f < NS) crec[o] = cr;
+	}
+	if (have) {
 		const float4 ra = make_float4(x0, y0, x1, y1), rb = make_float4(x2, y2, z0, z1), rc = make_float4(z2, 0.f, 0.f, 0.f);
 		frec[o * 3 + 0] = ra; frec[o * 3 + 1] = rb; frec[o * 3 + 2] = rc;
 		const float br = sqrtf(blur_radius);
@@ -409,7 +487,7 @@ __global__ void face_setup_kernel(const float* __restrict__ vproj, const int32_t
 		store_rec(recs + o, r);
 		const bool all_behind = z0 < z_clip && z1 < z_clip && z2 < z_clip;
 		const bool any_behind = z0 < z_clip || z1 < z_clip || z2 < z_clip;
-		if (any_behind && !all_behind) atomicAdd(&flags[0], 1);  // straddling the clip plane: PyTorch3D would clip it (clip.py)
+		if (any_behind && !all_behind) atomicAdd(&flags[0], 1);  // straddling the clip plane: PyTorch3D would clip it (clip.py; SPLIT: never)
 		const float zmax = fmaxf(z0, fmaxf(z1, z2));
 		const float area = edge_fn(x0, y0, x1, y1, x2, y2);
 		const bool degenerate = area <= KEPS && area >= -KEPS;
@@ -425,7 +503,7 @@ __global__ void face_setup_kernel(const float* __restrict__ vproj, const int32_t
 			}
 		}
 	}
-	if (f < F) { tb[o] = packed; fzmin[o] = zmn; }
+	if (f < NS) { tb[o] = packed; fzmin[o] = zmn; }
 	// per wave: the tile bbox of its 64 consecutive faces (the binning waves test these first and only open the runs that reach their
 	// tile: faces that are neighbours in the index are neighbours on the surface in any mesh that was not shuffled on purpose), and
 	// their depth statistics
@@ -440,8 +518,8 @@ __global__ void face_setup_kernel(const float* __restrict__ vproj, const int32_t
 		zlo = min(zlo, (uint32_t)__shfl_xor((int)zlo, d, 64)); zhi = max(zhi, (uint32_t)__shfl_xor((int)zhi, d, 64));
 		zex = max(zex, (uint32_t)__shfl_xor((int)zex, d, 64));
 	}
-	if ((threadIdx.x & 63) == 0 && f < F) {
-		const int64_t ro = (int64_t)img * ((F + 63) / 64) + f / 64;
+	if ((threadIdx.x & 63) == 0 && f < NS) {
+		const int64_t ro = (int64_t)img * ((NS + 63) / 64) + f / 64;
 		tbb[ro] = bx0 > bx1 ? TB_EMPTY : ((uint32_t)bx0 | ((uint32_t)bx1 << 8) | ((uint32_t)by0 << 16) | ((uint32_t)by1 << 24));
 		rz[ro * 4] = zlo; rz[ro * 4 + 1] = zhi; rz[ro * 4 + 2] = zex; rz[ro * 4 + 3] = 0u;
 	}
@@ -1170,6 +1248,34 @@ __global__ __launch_bounds__(256) void raster_kernel(const RasterArgs a, const F
 #include "render_band.h"
 
 
+// clip_faces = 1: the nearest inside fragment of every pixel came from a SLOT (a clipped triangle of a face); before anything is shaded or
+// handed out, its id becomes the original face's and its barycentrics the original face's (PyTorch3D's
+// convert_clipped_rasterization_to_original_faces).  Depth and distance stay the clipped triangle's.  The slot goes to p2s for the RGB
+// backward.  A slot that holds its face unclipped keeps its barycentrics bit for bit.
+__global__ __launch_bounds__(256) void clip_frag_kernel(int64_t n_px, int64_t hw, int F, const float4* __restrict__ crec, int32_t* __restrict__ p2f_ws,
+														 float* __restrict__ frag_ws, int32_t* __restrict__ p2s) {
+	const int64_t pix = (int64_t)blockIdx.x * 256 + threadIdx.x;
+	if (pix >= n_px) return;
+	const int s = p2f_ws[pix];
+	p2s[pix] = s;
+	if (s < 0) return;
+	const int64_t img = pix / hw;
+	p2f_ws[pix] = s >= F ? s - F : s;
+	const float4 cr = crec[img * 2 * F + s];
+	const uint32_t pk = __float_as_uint(cr.w);
+	if (!(pk & CLIP_SPLIT)) return;
+	float* fr = frag_ws + pix * 8;
+	const float b[3] = {fr[0], fr[1], fr[2]}, cw[3] = {cr.x, cr.y, cr.z};
+	float o[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+	for (int k = 0; k < 3; ++k) {
+		const int ea = (pk >> (4 * k)) & 3, eb = (pk >> (4 * k + 2)) & 3;
+		o[ea] += b[k] * (1.0f - cw[k]);
+		o[eb] += b[k] * cw[k];
+	}
+	fr[0] = o[0]; fr[1] = o[1]; fr[2] = o[2];
+}
+
 // Phong shading + softmax blend (K = 1) of every pixel's nearest inside fragment, the user-visible pix_to_face / zbuf, and the
 // barycentrics the RGB backward reads: one thread per pixel of the tiles that have a list (the others got their background from bin_kernel).
 __global__ __launch_bounds__(256) void shade_kernel(const TileArgs a) {
@@ -1316,11 +1422,14 @@ __global__ __launch_bounds__(256) void tie_fix_kernel(const TileArgs a, const Fa
 // divergence between faces with different bbox sizes), accumulate the gradients of its three NDC vertices in registers
 // (PointTriangleDistanceBackward: nearest edge only, projection parameter treated as constant), butterfly-reduce them, and
 // lane 0 issues the six atomics.
-template <int LPF>
+// SPLIT (clip_faces = 1): F counts the SLOTS (2 x the faces); a slot that holds a clipped triangle leaves its gradients in d_sub
+// (clip_chain_kernel takes them to the face's vertices), a slot that holds its face unclipped adds them to d_vproj as the default mode does.
+template <int LPF, bool SPLIT>
 __global__ __launch_bounds__(256) void sil_bwd_kernel(const find_render_params rp, const FaceRec* __restrict__ recs, const uint32_t* __restrict__ tb,
 													   const int32_t* __restrict__ faces, int64_t faces_mesh_stride, int n_views, int V, int F,
 													   const float* __restrict__ alpha_ws, const float* __restrict__ d_mask, const float* __restrict__ zthr,
-													   const int32_t* __restrict__ tie_face, float* __restrict__ d_vproj) {
+													   const int32_t* __restrict__ tie_face, float* __restrict__ d_vproj, const float4* __restrict__ crec,
+													   float* __restrict__ d_sub) {
 	const int img = blockIdx.y;
 	const int sub = threadIdx.x & (LPF - 1);
 	const int f = blockIdx.x * (256 / LPF) + threadIdx.x / LPF;
@@ -1406,8 +1515,15 @@ __global__ __launch_bounds__(256) void sil_bwd_kernel(const find_render_params r
 		g1y += __shfl_xor(g1y, d, 64); g2x += __shfl_xor(g2x, d, 64); g2y += __shfl_xor(g2y, d, 64);
 	}
 	if (!act || sub != 0) return;
+	if constexpr (SPLIT) {
+		if (__float_as_uint(crec[o].w) & CLIP_SPLIT) {
+			float* ds = d_sub + o * 12;
+			ds[0] += g0x; ds[1] += g0y; ds[3] += g1x; ds[4] += g1y; ds[6] += g2x; ds[7] += g2y;
+			return;
+		}
+	}
 	const int mesh = img / n_views;
-	const int32_t* fp = faces + (int64_t)mesh * faces_mesh_stride + (int64_t)f * 3;
+	const int32_t* fp = faces + (int64_t)mesh * faces_mesh_stride + (int64_t)f * 3;   // (SPLIT: an unclipped slot is its face, f < F / 2)
 	float* dv = d_vproj + (int64_t)img * V * 3;
 	if (g0x != 0.f || g0y != 0.f) { atomicAdd(dv + 3 * fp[0], g0x); atomicAdd(dv + 3 * fp[0] + 1, g0y); }
 	if (g1x != 0.f || g1y != 0.f) { atomicAdd(dv + 3 * fp[1], g1x); atomicAdd(dv + 3 * fp[1] + 1, g1y); }
@@ -1446,10 +1562,32 @@ __device__ __forceinline__ void rgb_grad_commit(const RgbGrad& o, const int32_t*
 	}
 }
 
-// gradient contribution of ONE pixel whose nearest fragment is face bf (barycentrics bw, upstream gradient g), added into o
+// SPLIT: a slot that holds a clipped triangle hands the NDC part (o.g: its own vertices; dw: its w_k) to d_sub, the rest as above
+__device__ __forceinline__ void rgb_grad_commit_split(const RgbGrad& o, const float* dw, bool clipped, const int32_t* fp, int64_t mesh, int64_t img, int V,
+													  float* d_vproj, float* d_verts, float* d_normals, float* d_colors, float* ds) {
+	if (!clipped) { rgb_grad_commit(o, fp, mesh, img, V, d_vproj, d_verts, d_normals, d_colors); return; }
+#pragma unroll
+	for (int k = 0; k < 3; ++k) {
+		const int64_t vo = (mesh * V + fp[k]) * 3;
+#pragma unroll
+		for (int c = 0; c < 3; ++c) {
+			atomicAdd(d_verts + vo + c, o.dP[k][c]);
+			atomicAdd(d_normals + vo + c, o.dN[k][c]);
+			if (d_colors) atomicAdd(d_colors + vo + c, o.dC[k][c]);
+			atomicAdd(ds + 3 * k + c, o.g[3 * k + c]);
+		}
+		atomicAdd(ds + 9 + k, dw[k]);
+	}
+}
+
+// gradient contribution of ONE pixel whose nearest fragment is face bf (barycentrics bw, upstream gradient g), added into o.
+// SPLIT: bf is a slot of F (frec is the clipped triangle's), fp / bw are the original face's; when the slot holds a clipped triangle (cr)
+// the barycentric gradient is taken to the triangle's own barycentrics, o.g receives its vertices' gradients, dw those of its w_k.
+template <bool SPLIT = false>
 __device__ __forceinline__ void rgb_pixel_grad(const find_render_params& rp, const float4* __restrict__ frec, const int32_t* fp, const float* __restrict__ verts,
 											   const float* __restrict__ normals, const float* __restrict__ colors, const float* __restrict__ cam, int mesh,
-											   int view, int64_t img, int V, int F, int bf, int xi, int yi, const float* g, const float* bw, RgbGrad& o) {
+											   int view, int64_t img, int V, int F, int bf, int xi, int yi, const float* g, const float* bw, RgbGrad& o,
+											   float4 cr = float4{}, float* dw = nullptr) {
 	const int H = rp.image_h, W = rp.image_w;
 	float P[3][3], N[3][3], C[3][3];
 	float pos[3] = {0, 0, 0}, nrm[3] = {0, 0, 0}, tex[3] = {0, 0, 0};
@@ -1529,6 +1667,19 @@ __device__ __forceinline__ void rgb_pixel_grad(const find_render_params& rp, con
 	const float den = t0 + t1 + t2;
 	if (!(den > KEPS)) return;  // (degenerate fragment: only the interpolation part contributes)
 	const float inv_den = 1.0f / den;
+	if constexpr (SPLIT) {
+		const uint32_t pk = __float_as_uint(cr.w);
+		if (pk & CLIP_SPLIT) {
+			// original barycentrics = sum_k b_k [(1 - w_k) e_a + w_k e_b], b_k = t_k / den the clipped triangle's
+			const float cw[3] = {cr.x, cr.y, cr.z}, bk[3] = {t0 * inv_den, t1 * inv_den, t2 * inv_den}, dbo[3] = {d_bw[0], d_bw[1], d_bw[2]};
+#pragma unroll
+			for (int k = 0; k < 3; ++k) {
+				const int ea = (pk >> (4 * k)) & 3, eb = (pk >> (4 * k + 2)) & 3;
+				d_bw[k] = dbo[ea] * (1.0f - cw[k]) + dbo[eb] * cw[k];
+				dw[k] += bk[k] * (dbo[eb] - dbo[ea]);
+			}
+		}
+	}
 	const float sdb = (d_bw[0] * t0 + d_bw[1] * t1 + d_bw[2] * t2) * inv_den;
 	const float d_t0 = (d_bw[0] - sdb) * inv_den, d_t1 = (d_bw[1] - sdb) * inv_den, d_t2 = (d_bw[2] - sdb) * inv_den;
 	const float d_w0 = d_t0 * z1 * z2, d_w1 = d_t1 * z0 * z2, d_w2 = d_t2 * z0 * z1;
@@ -1587,6 +1738,38 @@ __global__ __launch_bounds__(256) void rgb_bwd_kernel(const find_render_params r
 	rgb_grad_commit(o, fp, mesh, img, V, d_vproj, d_verts, d_normals, d_colors);
 }
 
+// clip_faces = 1: rgb_bwd_kernel over slots -- F counts the slots, p2f holds slots (p2s), bary the original face's barycentrics.
+__global__ __launch_bounds__(256) void rgb_bwd_split_kernel(const find_render_params rp, const float4* __restrict__ frec,
+													   const int32_t* __restrict__ faces, int64_t faces_mesh_stride,
+													   const float* __restrict__ verts, const float* __restrict__ normals,
+													   const float* __restrict__ colors, const float* __restrict__ cam, int n_views,
+													   int V, int F, const int32_t* __restrict__ p2f, const float* __restrict__ bary,
+													   const float* __restrict__ d_image, float* __restrict__ d_vproj,
+													   float* __restrict__ d_verts, float* __restrict__ d_normals,
+													   float* __restrict__ d_colors, const float4* __restrict__ crec, float* __restrict__ d_sub) {
+	const int H = rp.image_h, W = rp.image_w;
+	const int img = blockIdx.y;
+	const int p = blockIdx.x * blockDim.x + threadIdx.x;
+	if (p >= H * W) return;
+	const int64_t pix = (int64_t)img * H * W + p;
+	const int bf = p2f[pix];
+	if (bf < 0) return;
+	const float g[3] = {d_image[pix * 3], d_image[pix * 3 + 1], d_image[pix * 3 + 2]};
+	if (g[0] == 0.f && g[1] == 0.f && g[2] == 0.f) return;
+	const int mesh = img / n_views, view = img - mesh * n_views;
+	const float bw[3] = {bary[pix * 3], bary[pix * 3 + 1], bary[pix * 3 + 2]};
+	RgbGrad o;
+	rgb_grad_zero(o);
+	{
+		const int32_t* fp = faces + (int64_t)mesh * faces_mesh_stride + (int64_t)(bf >= F / 2 ? bf - F / 2 : bf) * 3;
+		const int64_t so = (int64_t)img * F + bf;
+		const float4 cr = crec[so];
+		float dw[3] = {0.f, 0.f, 0.f};
+		rgb_pixel_grad<true>(rp, frec, fp, verts, normals, colors, cam, mesh, view, img, V, F, bf, p % W, p / W, g, bw, o, cr, dw);
+		rgb_grad_commit_split(o, dw, __float_as_uint(cr.w) & CLIP_SPLIT, fp, mesh, img, V, d_vproj, d_verts, d_normals, d_colors, d_sub + so * 12);
+	}
+}
+
 // Face-centric variant for large images (a visible face covers several pixels): one thread per (image, face) walks the
 // face's pixel bbox, sums the contributions of the pixels whose nearest fragment it is, and issues its 36 atomics ONCE.
 __global__ __launch_bounds__(256) void rgb_bwd_faces_kernel(const find_render_params rp, const float4* __restrict__ frec, const uint32_t* __restrict__ tb,
@@ -1623,6 +1806,96 @@ __global__ __launch_bounds__(256) void rgb_bwd_faces_kernel(const find_render_pa
 			any = true;
 		}
 	if (any) rgb_grad_commit(o, fp, mesh, img, V, d_vproj, d_verts, d_normals, d_colors);
+}
+
+// clip_faces = 1: rgb_bwd_faces_kernel over slots -- one thread per SLOT (F counts the slots, p2f holds slots: p2s).
+__global__ __launch_bounds__(256) void rgb_bwd_faces_split_kernel(const find_render_params rp, const float4* __restrict__ frec, const uint32_t* __restrict__ tb,
+															 const int32_t* __restrict__ faces, int64_t faces_mesh_stride,
+															 const float* __restrict__ verts, const float* __restrict__ normals,
+															 const float* __restrict__ colors, const float* __restrict__ cam, int n_views,
+															 int V, int F, const int32_t* __restrict__ p2f, const float* __restrict__ bary,
+															 const float* __restrict__ d_image, float* __restrict__ d_vproj,
+															 float* __restrict__ d_verts, float* __restrict__ d_normals,
+															 float* __restrict__ d_colors, const float4* __restrict__ crec, float* __restrict__ d_sub) {
+	const int H = rp.image_h, W = rp.image_w;
+	const int img = blockIdx.y;
+	const int f = blockIdx.x * blockDim.x + threadIdx.x;
+	if (f >= F) return;
+	const int64_t fo = (int64_t)img * F + f;
+	if (tb[fo] == TB_EMPTY) return;
+	const float4 fa = frec[fo * 3], fb = frec[fo * 3 + 1];
+	int xlo, xhi, ylo, yhi;
+	pix_range(fminf(fa.x, fminf(fa.z, fb.x)), fmaxf(fa.x, fmaxf(fa.z, fb.x)), W, &xlo, &xhi);
+	pix_range(fminf(fa.y, fminf(fa.w, fb.y)), fmaxf(fa.y, fmaxf(fa.w, fb.y)), H, &ylo, &yhi);
+	const int mesh = img / n_views, view = img - mesh * n_views;
+	const int32_t* fp = faces + (int64_t)mesh * faces_mesh_stride + (int64_t)(f >= F / 2 ? f - F / 2 : f) * 3;
+	RgbGrad o;
+	rgb_grad_zero(o);
+	const float4 cr = crec[fo];
+	float dw[3] = {0.f, 0.f, 0.f};
+	bool any = false;
+	for (int yi = ylo; yi <= yhi; ++yi)
+		for (int xi = xlo; xi <= xhi; ++xi) {
+			const int64_t pix = ((int64_t)img * H + yi) * W + xi;
+			if (p2f[pix] != f) continue;
+			const float g[3] = {d_image[pix * 3], d_image[pix * 3 + 1], d_image[pix * 3 + 2]};
+			if (g[0] == 0.f && g[1] == 0.f && g[2] == 0.f) continue;
+			const float bw[3] = {bary[pix * 3], bary[pix * 3 + 1], bary[pix * 3 + 2]};
+			rgb_pixel_grad<true>(rp, frec, fp, verts, normals, colors, cam, mesh, view, img, V, F, f, xi, yi, g, bw, o, cr, dw);
+			any = true;
+		}
+	if (!any) return;
+	rgb_grad_commit_split(o, dw, __float_as_uint(cr.w) & CLIP_SPLIT, fp, mesh, img, V, d_vproj, d_verts, d_normals, d_colors, d_sub + fo * 12);
+}
+
+// clip_faces = 1: the gradients a clipped face's slots collected for their own vertices (d_sub: x, y, z of each, and the w_k of the
+// barycentric conversion) go to the face's vertices through the clip (clip_slot): a new vertex on edge (a, b) has
+// xy = ((1 - w) xy_a z_a + w xy_b z_b) / zc, z = zc (a constant: its depth gradient ends here) and w = (zc - z_a) / (z_b - z_a), so
+// dw / dz_a = -(1 - w) / (z_b - z_a), dw / dz_b = -w / (z_b - z_a).  One thread per (image, face); its slots f and F + f.
+__global__ void clip_chain_kernel(const float* __restrict__ vproj, const int32_t* __restrict__ faces, int64_t faces_mesh_stride, int n_views, int V, int F,
+								  float zc, const float4* __restrict__ crec, const float* __restrict__ d_sub, float* __restrict__ d_vproj) {
+	const int img = blockIdx.y;
+	const int f = blockIdx.x * blockDim.x + threadIdx.x;
+	if (f >= F) return;
+	const int64_t o0 = (int64_t)img * 2 * F + f;
+	if (!(__float_as_uint(crec[o0].w) & CLIP_SPLIT)) return;   // unclipped, culled or padding: nothing here
+	const int32_t* fp = faces + (int64_t)(img / n_views) * faces_mesh_stride + (int64_t)f * 3;
+	const float* vp = vproj + (int64_t)img * V * 3;
+	float X[3], Y[3], Z[3], G[9];
+#pragma unroll
+	for (int i = 0; i < 3; ++i) { X[i] = vp[3 * fp[i]]; Y[i] = vp[3 * fp[i] + 1]; Z[i] = vp[3 * fp[i] + 2]; }
+#pragma unroll
+	for (int i = 0; i < 9; ++i) G[i] = 0.f;
+	const float izc = 1.0f / zc;
+	for (int h = 0; h < 2; ++h) {
+		const int64_t so = o0 + (int64_t)h * F;
+		const float4 cr = crec[so];
+		const uint32_t pk = __float_as_uint(cr.w);
+		if (!(pk & CLIP_SPLIT)) continue;
+		const float* ds = d_sub + so * 12;
+		const float cw[3] = {cr.x, cr.y, cr.z};
+#pragma unroll
+		for (int k = 0; k < 3; ++k) {
+			const int a = (pk >> (4 * k)) & 3, b = (pk >> (4 * k + 2)) & 3;
+			const float gx = ds[3 * k], gy = ds[3 * k + 1], gz = ds[3 * k + 2];
+			if (a == b) { G[3 * a] += gx; G[3 * a + 1] += gy; G[3 * a + 2] += gz; continue; }
+			const float w = cw[k], u = 1.0f - w;
+			G[3 * a] += gx * u * Z[a] * izc; G[3 * a + 1] += gy * u * Z[a] * izc;
+			G[3 * b] += gx * w * Z[b] * izc; G[3 * b + 1] += gy * w * Z[b] * izc;
+			G[3 * a + 2] += (gx * X[a] + gy * Y[a]) * u * izc;
+			G[3 * b + 2] += (gx * X[b] + gy * Y[b]) * w * izc;
+			const float dW = ds[9 + k] + (gx * (X[b] * Z[b] - X[a] * Z[a]) + gy * (Y[b] * Z[b] - Y[a] * Z[a])) * izc;
+			const float idz = 1.0f / (Z[b] - Z[a]);
+			G[3 * a + 2] -= dW * u * idz;
+			G[3 * b + 2] -= dW * w * idz;
+		}
+	}
+	float* dv = d_vproj + (int64_t)img * V * 3;
+#pragma unroll
+	for (int i = 0; i < 3; ++i)
+#pragma unroll
+		for (int c = 0; c < 3; ++c)
+			if (G[3 * i + c] != 0.f) atomicAdd(dv + 3 * fp[i] + c, G[3 * i + c]);
 }
 
 // vertex-normal backward: n_v = normalize(sum_f fn_f), fn_f = (v2 - v1) x (v0 - v1).  d_normals holds dL/dn_v.
@@ -1689,6 +1962,8 @@ static int check_params(const find_render_params* rp, int64_t n_meshes, int64_t 
 	FIND_REQUIRE(n_meshes >= 1 && n_views >= 1 && n_views <= 256 && n_meshes * n_views < 65536, "find_render: bad batch (%lld meshes x %lld views)", (long long)n_meshes, (long long)n_views);
 	FIND_REQUIRE(V >= 1 && F >= 1 && V < (1ll << 28) && F < (1ll << 24), "find_render: bad mesh size (a tile list entry holds the face index in 24 bits)");
 	FIND_REQUIRE(rp->sil_sigma > 0.f && rp->rgb_sigma > 0.f && rp->rgb_gamma > 0.f && rp->zfar > rp->znear, "find_render: bad blend parameters");
+	FIND_REQUIRE(rp->clip_faces == 0 || rp->clip_faces == 1, "find_render: clip_faces must be 0 or 1");
+	FIND_REQUIRE(!rp->clip_faces || (F < (1ll << 23) && rp->z_clip > 0.f), "find_render: clip_faces = 1 needs z_clip > 0 and fewer than 2^23 faces (2 slots per face in a 24-bit list entry)");
 	return FIND_OK;
 }
 
@@ -1723,9 +1998,16 @@ extern "C" int find_render_fwd(const find_render_params* rp, const float* verts,
 	// the silhouette's blur margin is a superset of the RGB pass's (blur 0); one set of lists serves both
 	const float blur = mask ? rp->sil_blur_radius : 0.0f;
 	const int tiles_x = (int)cdiv(W, T8), tiles_per_img = tiles_x * (int)cdiv(H, T8);
-	const int n_runs = (int)cdiv(F, 64);
-	hipLaunchKernelGGL(face_setup_kernel, dim3((unsigned)cdiv(F, 256), (unsigned)n_img), dim3(256), 0, s, w.vproj, faces, fstride, (int)n_views, V, F, H, W,
-					   blur, rp->z_clip, w.frec, w.recs, w.tb, w.tbb, w.fzmin, w.rz, w.flags);
+	// clip_faces = 1: from here on the binning, the rasterisers and the tie fix-up see NS = 2 F face slots per image (the clipped triangles)
+	const bool split = rp->clip_faces != 0;
+	const int NS = (int)w.n_slots;
+	const int n_runs = (int)cdiv(NS, 64);
+	if (split)
+		hipLaunchKernelGGL(face_setup_kernel<true>, dim3((unsigned)cdiv(NS, 256), (unsigned)n_img), dim3(256), 0, s, w.vproj, faces, fstride, (int)n_views, V, F, H, W,
+						   blur, rp->z_clip, w.frec, w.recs, w.tb, w.tbb, w.fzmin, w.rz, w.flags, w.crec);
+	else
+		hipLaunchKernelGGL(face_setup_kernel<false>, dim3((unsigned)cdiv(F, 256), (unsigned)n_img), dim3(256), 0, s, w.vproj, faces, fstride, (int)n_views, V, F, H, W,
+						   blur, rp->z_clip, w.frec, w.recs, w.tb, w.tbb, w.fzmin, w.rz, w.flags, nullptr);
 	hipLaunchKernelGGL(zinfo_kernel, dim3((unsigned)n_img), dim3(256), 0, s, w.tbb, w.rz, n_runs, w.zinfo);
 	if (image) {
 		(void)hipMemsetAsync(w.normals, 0, n_meshes * n_verts * 3 * sizeof(float), s);
@@ -1739,7 +2021,7 @@ extern "C" int find_render_fwd(const find_render_params* rp, const float* verts,
 	a.rp = *rp;
 	a.tb = w.tb; a.tbb = w.tbb; a.fzmin = w.fzmin; a.zinfo = w.zinfo; a.faces = faces; a.faces_mesh_stride = fstride;
 	a.verts = verts; a.normals = w.normals; a.colors = vert_colors; a.cam = cam;
-	a.n_views = (int)n_views; a.V = V; a.F = F; a.tiles_x = tiles_x;
+	a.n_views = (int)n_views; a.V = V; a.F = NS; a.tiles_x = tiles_x;
 	a.mask = mask; a.image = image; a.p2f_out = pix_to_face; a.zbuf_out = zbuf;
 	a.p2f_ws = (image || pix_to_face || zbuf) ? w.p2f : nullptr; a.bary_ws = w.bary; a.frag_ws = w.frag; a.flags = w.flags; a.qn = w.qn; a.cursor = w.cursor;
 	a.zthr = w.zthr; a.alpha_ws = w.alpha; a.tie_face = w.tie_face; a.scratch = w.scratch;
@@ -1753,7 +2035,7 @@ extern "C" int find_render_fwd(const find_render_params* rp, const float* verts,
 	RasterArgs ra;
 	memset(&ra, 0, sizeof(ra));
 	ra.sil_blur_radius = rp->sil_blur_radius; ra.sil_sigma = rp->sil_sigma; ra.sil_faces_per_pixel = rp->sil_faces_per_pixel; ra.image_h = H; ra.image_w = W;
-	ra.tb = w.tb; ra.zinfo = w.zinfo; ra.tinfo = w.tinfo; ra.F = F; ra.tiles_x = tiles_x; ra.tiles_per_img = tiles_per_img; ra.pool_cap = w.pool_cap;
+	ra.tb = w.tb; ra.zinfo = w.zinfo; ra.tinfo = w.tinfo; ra.F = NS; ra.tiles_x = tiles_x; ra.tiles_per_img = tiles_per_img; ra.pool_cap = w.pool_cap;
 	ra.mask = mask; ra.p2f_ws = a.p2f_ws; ra.frag_ws = w.frag; ra.flags = w.flags; ra.qn = w.qn; ra.zthr = w.zthr; ra.alpha_ws = w.alpha;
 	ra.scratch = w.scratch; ra.fix = w.fix; ra.ablate = a.ablate;
 	// Which rasteriser: the list-free band kernel (render_band.h) from BAND_MIN_PIXELS pixels per image on, the candidate-list kernel below
@@ -1772,7 +2054,13 @@ extern "C" int find_render_fwd(const find_render_params* rp, const float* verts,
 	} else if (mask && a.p2f_ws) hipLaunchKernelGGL((raster_kernel<true, true>), dim3((unsigned)w.raster_wgs), dim3(256), 0, s, ra, w.recs, w.pool, w.order);
 	else if (mask) hipLaunchKernelGGL((raster_kernel<true, false>), dim3((unsigned)w.raster_wgs), dim3(256), 0, s, ra, w.recs, w.pool, w.order);
 	else hipLaunchKernelGGL((raster_kernel<false, true>), dim3((unsigned)w.raster_wgs), dim3(256), 0, s, ra, w.recs, w.pool, w.order);
-	if (a.p2f_ws) hipLaunchKernelGGL(shade_kernel, dim3((unsigned)cdiv(n_img * H * W, 256)), dim3(256), 0, s, a);
+	if (a.p2f_ws && split) {
+		// slots -> original faces and their barycentrics, before anything reads them; shading and pix_to_face count faces
+		hipLaunchKernelGGL(clip_frag_kernel, dim3((unsigned)cdiv(n_img * H * W, 256)), dim3(256), 0, s, n_img * H * W, (int64_t)H * W, F, w.crec, w.p2f, w.frag, w.p2s);
+		TileArgs af = a;
+		af.F = F;
+		hipLaunchKernelGGL(shade_kernel, dim3((unsigned)cdiv(n_img * H * W, 256)), dim3(256), 0, s, af);
+	} else if (a.p2f_ws) hipLaunchKernelGGL(shade_kernel, dim3((unsigned)cdiv(n_img * H * W, 256)), dim3(256), 0, s, a);
 	if (mask) hipLaunchKernelGGL(tie_fix_kernel, dim3(256), dim3(256), 0, s, a, w.recs);
 	FIND_LAUNCH_CHECK("find_render_fwd");
 	return FIND_OK;
@@ -1799,25 +2087,44 @@ extern "C" int find_render_bwd(const find_render_params* rp, const float* verts,
 	const float sc = 1.0f / tanf(rp->fov_deg * 3.14159265358979323846f / 180.0f * 0.5f);
 	(void)hipMemsetAsync(w.d_vproj, 0, n_img * n_verts * 3 * sizeof(float), s);
 	(void)hipMemsetAsync(d_verts, 0, n_meshes * n_verts * 3 * sizeof(float), s);
+	const bool split = rp->clip_faces != 0;
+	const int NS = (int)w.n_slots;   // face slots per image (clip_faces = 1: 2 F)
+	if (split) (void)hipMemsetAsync(w.d_sub, 0, n_img * NS * 12 * sizeof(float), s);
 	if (d_vert_colors) (void)hipMemsetAsync(d_vert_colors, 0, n_meshes * n_verts * 3 * sizeof(float), s);
 	if (d_mask) {
 		// lanes per face by the size of a typical blurred bbox (a face of ~1 px plus the blur margin on both sides)
 		const float side = 2.0f * sqrtf(rp->sil_blur_radius) * 0.5f * (float)std::max(H, W) + 2.0f;
 		// (8 lanes per face up to ~12 x 12 pixels, 16 up to ~25 x 25 -- 512^2: 17.5 x 17.5, measured 1 % of the C4 step better than 32 --, 32 above)
-		if (side * side > 640.0f)
-			hipLaunchKernelGGL(sil_bwd_kernel<32>, dim3((unsigned)cdiv(F, 8), (unsigned)n_img), dim3(256), 0, s, *rp, w.recs, w.tb, faces, fstride, (int)n_views, V, F,
-							   w.alpha, d_mask, w.zthr, w.tie_face, w.d_vproj);
+		if (split) {
+			if (side * side > 640.0f)
+				hipLaunchKernelGGL((sil_bwd_kernel<32, true>), dim3((unsigned)cdiv(NS, 8), (unsigned)n_img), dim3(256), 0, s, *rp, w.recs, w.tb, faces, fstride, (int)n_views, V, NS,
+								   w.alpha, d_mask, w.zthr, w.tie_face, w.d_vproj, w.crec, w.d_sub);
+			else if (side * side > 160.0f)
+				hipLaunchKernelGGL((sil_bwd_kernel<16, true>), dim3((unsigned)cdiv(NS, 16), (unsigned)n_img), dim3(256), 0, s, *rp, w.recs, w.tb, faces, fstride, (int)n_views, V, NS,
+								   w.alpha, d_mask, w.zthr, w.tie_face, w.d_vproj, w.crec, w.d_sub);
+			else
+				hipLaunchKernelGGL((sil_bwd_kernel<8, true>), dim3((unsigned)cdiv(NS, 32), (unsigned)n_img), dim3(256), 0, s, *rp, w.recs, w.tb, faces, fstride, (int)n_views, V, NS,
+								   w.alpha, d_mask, w.zthr, w.tie_face, w.d_vproj, w.crec, w.d_sub);
+		} else if (side * side > 640.0f)
+			hipLaunchKernelGGL((sil_bwd_kernel<32, false>), dim3((unsigned)cdiv(F, 8), (unsigned)n_img), dim3(256), 0, s, *rp, w.recs, w.tb, faces, fstride, (int)n_views, V, F,
+							   w.alpha, d_mask, w.zthr, w.tie_face, w.d_vproj, nullptr, nullptr);
 		else if (side * side > 160.0f)
-			hipLaunchKernelGGL(sil_bwd_kernel<16>, dim3((unsigned)cdiv(F, 16), (unsigned)n_img), dim3(256), 0, s, *rp, w.recs, w.tb, faces, fstride, (int)n_views, V, F,
-							   w.alpha, d_mask, w.zthr, w.tie_face, w.d_vproj);
+			hipLaunchKernelGGL((sil_bwd_kernel<16, false>), dim3((unsigned)cdiv(F, 16), (unsigned)n_img), dim3(256), 0, s, *rp, w.recs, w.tb, faces, fstride, (int)n_views, V, F,
+							   w.alpha, d_mask, w.zthr, w.tie_face, w.d_vproj, nullptr, nullptr);
 		else
-			hipLaunchKernelGGL(sil_bwd_kernel<8>, dim3((unsigned)cdiv(F, 32), (unsigned)n_img), dim3(256), 0, s, *rp, w.recs, w.tb, faces, fstride, (int)n_views, V, F,
-						   w.alpha, d_mask, w.zthr, w.tie_face, w.d_vproj);
+			hipLaunchKernelGGL((sil_bwd_kernel<8, false>), dim3((unsigned)cdiv(F, 32), (unsigned)n_img), dim3(256), 0, s, *rp, w.recs, w.tb, faces, fstride, (int)n_views, V, F,
+						   w.alpha, d_mask, w.zthr, w.tie_face, w.d_vproj, nullptr, nullptr);
 	}
 	if (d_image) {
 		(void)hipMemsetAsync(w.d_normals, 0, n_meshes * n_verts * 3 * sizeof(float), s);
 		// sum per face before the atomics unless faces vastly outnumber pixels (measured: faster even at about one pixel per visible face)
-		if ((int64_t)H * W * 2 >= (int64_t)F)
+		if (split && (int64_t)H * W * 2 >= (int64_t)F)   // (the slot arrays, the slots' nearest-fragment map p2s)
+			hipLaunchKernelGGL(rgb_bwd_faces_split_kernel, dim3((unsigned)cdiv(NS, 256), (unsigned)n_img), dim3(256), 0, s, *rp, w.frec, w.tb, faces, fstride, verts, w.normals,
+							   vert_colors, cam, (int)n_views, V, NS, w.p2s, w.bary, d_image, w.d_vproj, d_verts, w.d_normals, d_vert_colors, w.crec, w.d_sub);
+		else if (split)
+			hipLaunchKernelGGL(rgb_bwd_split_kernel, dim3((unsigned)cdiv((int64_t)H * W, 256), (unsigned)n_img), dim3(256), 0, s, *rp, w.frec, faces, fstride, verts,
+							   w.normals, vert_colors, cam, (int)n_views, V, NS, w.p2s, w.bary, d_image, w.d_vproj, d_verts, w.d_normals, d_vert_colors, w.crec, w.d_sub);
+		else if ((int64_t)H * W * 2 >= (int64_t)F)
 			hipLaunchKernelGGL(rgb_bwd_faces_kernel, dim3((unsigned)cdiv(F, 256), (unsigned)n_img), dim3(256), 0, s, *rp, w.frec, w.tb, faces, fstride, verts, w.normals,
 							   vert_colors, cam, (int)n_views, V, F, w.p2f, w.bary, d_image, w.d_vproj, d_verts, w.d_normals, d_vert_colors);
 		else
@@ -1829,6 +2136,9 @@ extern "C" int find_render_bwd(const find_render_params* rp, const float* verts,
 		hipLaunchKernelGGL(normals_bwd_prepare_kernel, dim3((unsigned)cdiv(n_meshes * n_verts, 256)), dim3(256), 0, s, w.raw_normals, w.normals, w.d_normals, n_meshes * n_verts);
 		hipLaunchKernelGGL(normals_bwd_faces_kernel, dim3((unsigned)cdiv(F, 256), (unsigned)n_meshes), dim3(256), 0, s, verts, faces, fstride, V, F, w.d_normals, d_verts);
 	}
+	if (split && (d_mask || d_image))   // the clipped slots' gradients -> the vertices of their faces
+		hipLaunchKernelGGL(clip_chain_kernel, dim3((unsigned)cdiv(F, 256), (unsigned)n_img), dim3(256), 0, s, w.vproj, faces, fstride, (int)n_views, V, F, rp->z_clip,
+						   w.crec, w.d_sub, w.d_vproj);
 	hipLaunchKernelGGL(project_bwd_kernel, dim3((unsigned)cdiv(V, 256), (unsigned)n_meshes), dim3(256), 0, s, verts, R, T, sc, (int)n_views, V, w.d_vproj, d_verts, 1);
 	FIND_LAUNCH_CHECK("find_render_bwd");
 	return FIND_OK;

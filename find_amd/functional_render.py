@@ -14,8 +14,10 @@ from .functional import _c, _faces_i32, _require_gpu, _ws
 
 
 def make_params(image_size=256, faces_per_pixel=100, background=(1., 1., 1.), light_pos=(0., 0., 100.), znear=0.02, zfar=100.0,
-				fov_deg=60.0, sil_sigma=1e-4, z_clip=None):
-	"""FootRenderer's fixed settings (renderer.py:113-128, 274) + PyTorch3D defaults for BlendParams / PointLights / Materials."""
+				fov_deg=60.0, sil_sigma=1e-4, z_clip=None, clip_faces=False):
+	"""FootRenderer's fixed settings (renderer.py:113-128, 274) + PyTorch3D defaults for BlendParams / PointLights / Materials.
+	clip_faces: faces that straddle the z-clip plane are clipped into one or two triangles as PyTorch3D does (close-up views, a camera
+	inside the mesh); off (the default), they are rasterised whole and reported by the render watchdog below."""
 	p = RenderParams()
 	if isinstance(image_size, (tuple, list)):
 		p.image_h, p.image_w = int(image_size[0]), int(image_size[1])
@@ -24,18 +26,21 @@ def make_params(image_size=256, faces_per_pixel=100, background=(1., 1., 1.), li
 	p.fov_deg, p.znear, p.zfar = fov_deg, znear, zfar
 	p.sil_sigma = sil_sigma
 	p.sil_blur_radius = float(math.log(1. / 1e-4 - 1.) * sil_sigma)
+	if not 1 <= int(faces_per_pixel) <= 32767:   # (int16 in find_render_params: it shares its four bytes with clip_faces)
+		raise ValueError(f'make_params: faces_per_pixel {faces_per_pixel} outside 1 .. 32767')
 	p.sil_faces_per_pixel = faces_per_pixel
 	p.rgb_sigma, p.rgb_gamma = 1e-4, 1e-4
 	p.background[:] = list(background)
 	p.light_pos[:] = list(light_pos)
 	p.ambient, p.diffuse, p.specular, p.shininess = 0.5, 0.3, 0.2, 64.0
 	p.z_clip = znear / 2 if z_clip is None else z_clip
+	p.clip_faces = 1 if clip_faces else 0
 	return p
 
 
 # ---------------------------------------------------------------------------------------------- render watchdog
-# PyTorch3D clips faces that straddle the z-clip plane (znear / 2, renderer.py:231-234) into 1-2 triangles; this rasteriser does not:
-# it counts them (find_render_flags) and, like the pixels that collect more than 4096 silhouette candidates, they make the result differ
+# PyTorch3D clips faces that straddle the z-clip plane (znear / 2, renderer.py:231-234) into 1-2 triangles; this rasteriser does so only
+# with make_params(clip_faces=True) (FootRenderer(..., clip_faces=True)).  By default it counts them (find_render_flags) and, like the pixels that collect more than 4096 silhouette candidates, they make the result differ
 # from the reference.  Neither occurs with FIND's cameras (0.3 m from a <= 0.15 m object; view_from('toes') leaves 0.06 m).  A render
 # that hits either case is REPORTED: the two counters travel to a pinned host slot behind the launch and are looked at when they have
 # arrived -- at the next render call, in check_render_flags(), at an epoch boundary of find_amd.trainer.Trainer, or when the interpreter
@@ -70,7 +75,8 @@ def _report(vals, what, policy):
 		return
 	msg = (f'find_amd.render: {what}: {vals[0]} face(s) straddle the z-clip plane (PyTorch3D would clip them; this rasteriser '
 		   f'does not) and {vals[1]} pixel(s) collected more than 4096 silhouette candidates (K-nearest rule not applied): the '
-		   'result differs from the reference.  Move the camera; functional_render.FLAG_POLICY = "strict" / "ignore" changes this report.')
+		   'result differs from the reference.  Move the camera; functional_render.FLAG_POLICY = "strict" / "ignore" changes this report.'
+		   + ('  FootRenderer(..., clip_faces=True) / make_params(clip_faces=True) clips such faces as PyTorch3D does.' if vals[0] > 0 else ''))
 	if policy == 'warn':
 		warnings.warn(msg, RuntimeWarning, stacklevel=3)
 	else:

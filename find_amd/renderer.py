@@ -14,9 +14,12 @@ nn = torch.nn
 
 
 class FootRenderer(nn.Module):
-	def __init__(self, image_size, device='cuda', background_color=(1., 1., 1.), bin_size=None, z_clip_value=None, max_faces_per_bin=None):
+	def __init__(self, image_size, device='cuda', background_color=(1., 1., 1.), bin_size=None, z_clip_value=None, max_faces_per_bin=None,
+				 clip_faces=False):
 		"""bin_size / max_faces_per_bin are accepted for signature compatibility: binning is an acceleration structure of
-		PyTorch3D's CUDA rasteriser and must not change results; the HIP rasteriser tiles internally."""
+		PyTorch3D's CUDA rasteriser and must not change results; the HIP rasteriser tiles internally.
+		clip_faces (not in the reference): faces that straddle the z-clip plane are split as PyTorch3D's rasterize_meshes does (close-up
+		views, cameras inside the mesh); off, such a render is reported by functional_render's watchdog instead."""
 		super().__init__()
 		self.image_size = image_size
 		self.device = device
@@ -24,7 +27,7 @@ class FootRenderer(nn.Module):
 		self.bin_size, self.max_faces_per_bin = bin_size, max_faces_per_bin
 		self.light_location = (0., 0., 100.)  # PointLights(location=[[0, 0, 100]])  (renderer.py:114)
 		self.params = FR.make_params(image_size, faces_per_pixel=100, background=self.background_color, light_pos=self.light_location,
-									 znear=0.02, z_clip=z_clip_value)
+									 znear=0.02, z_clip=z_clip_value, clip_faces=clip_faces)
 
 	# ------------------------------------------------------------------ camera poses
 	# Every FIND camera looks along a ray through `at` with the world x axis as "up" (the foot's long axis; renderer.py:152,171,198).

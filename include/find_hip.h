@@ -397,7 +397,16 @@ typedef struct find_render_params {
 	float znear, zfar;    /* 0.02, 100 (renderer.py:274; PyTorch3D default zfar) */
 	float sil_blur_radius;/* log(1/1e-4 - 1) * 1e-4 (renderer.py:127) */
 	float sil_sigma;      /* 1e-4 (renderer.py:124) */
-	int32_t sil_faces_per_pixel; /* 100 (renderer.py:128); the soft mask uses the K nearest-in-depth faces */
+	int16_t sil_faces_per_pixel; /* 100 (renderer.py:128); the soft mask uses the K nearest-in-depth faces (1 .. 32767) */
+	int16_t clip_faces;   /* 0: a face that straddles the z-clip plane is rasterised whole and counted in find_render_flags' out2[0];
+	                       * 1: it is clipped as PyTorch3D's clip.py does (cull_to_frustum=False): one vertex behind the plane -> a quad
+	                       * split into two triangles, two behind -> one triangle; pix_to_face, the barycentrics (find_render_frags)
+	                       * and the shading refer to the original face, zbuf and the silhouette distances to the clipped triangle.
+	                       * Every image then has 2 x n_faces face slots (the second triangles of split quads after every face), so
+	                       * the workspace grows (find_render_ws_bytes), and n_faces must stay below 2^23.  No host synchronisation
+	                       * either way: both modes can be captured in a HIP graph.
+	                       * (The flag takes the upper half of what was an int32 K: the struct keeps its size and layout, and a
+	                       * caller that still writes K as an int32 gets clip_faces = 0 on this little-endian target.) */
 	float rgb_sigma, rgb_gamma;  /* 1e-4, 1e-4 BlendParams defaults */
 	float background[3];  /* (1,1,1) renderer.py:109,118 */
 	float light_pos[3];   /* (0,0,100) renderer.py:114 */
@@ -423,7 +432,8 @@ int find_render_bwd(const find_render_params* rp, const float* verts, const int3
 					int64_t n_verts, int64_t n_faces, const float* mask, const float* d_mask, const float* d_image,
 					float* d_verts, float* d_vert_colors, void* ws, int64_t ws_bytes, void* stream);
 /* Diagnostics of the last forward that used `ws` (synchronises the stream): out2[0] = faces straddling the z-clip
- * plane (PyTorch3D would clip them; they are rasterised whole here -- none exists on FIND's camera set-up),
+ * plane that were rasterised whole (clip_faces = 0; PyTorch3D would clip them -- none exists on FIND's camera set-up; always 0
+ * with clip_faces = 1),
  * out2[1] = pixels left UNRESOLVED by the K-nearest rule: a pixel with more silhouette candidates than
  * sil_faces_per_pixel keeps the K nearest in depth (ties to the earlier face, as PyTorch3D's per-pixel K-buffer);
  * only a pixel with more than 4096 candidates is not resolved -- all of its candidates stay blended. */
