@@ -1,7 +1,13 @@
 """Metric definitions of reference src/eval/eval_3d.py on the HIP path (row a16): keypoint error in mm (eval_3d.py:142,
 220-221), Chamfer over 10 000 surface samples reported x1e6 as "um" (eval_3d.py:148-151, 223 -- the reference's
 scaling of a m^2 quantity is kept) and the per-foot z <= 0.07 cut-off variant (eval_3d.py:154-161).
-Tables, plots, spins and OBJ export of the eval script are out of scope."""
+Tables, plots, spins and OBJ export of the eval script are out of scope.
+
+The 2-D half: MSE, PSNR, MSE_masked, PSNR_masked and IOU under the names and semantics of reference src/eval/eval_metrics.py (so that
+`from find_amd.eval_metrics import IOU, MSE, PSNR, MSE_masked, PSNR_masked` replaces that import), and eval_2d_metrics, the per-group
+metrics of eval_2d.py:86-121.  All of them are formed from the per-image sums of ONE pass over the images (FN.image_metric_sums), composed
+in float64 on the device; the scalar functions return float32 0-d tensors like their torch originals (MSE 0 -> PSNR inf, a union or mask
+sum of 0 -> nan)."""
 import torch
 
 from . import functional as FN
@@ -35,3 +41,93 @@ def eval_3d_metrics(pred_meshes, gt_meshes, pred_verts=None, template_kp_idxs=No
 		if template_kp_idxs is not None:
 			out['Keypoint (mm)'] = keypoint_error_mm(pred_verts, template_kp_idxs, gt_kps)
 	return out
+
+
+# ---------------------------------------------------------------------------------------------- 2-D (eval_2d.py, eval_metrics.py)
+SQ, SQ_EACH, SQ_COMMON, INTER, UNION, WSQ, W = range(7)   # columns of FN.image_metric_sums
+
+
+def _f32(t):
+	return t if t.dtype == torch.float32 else t.float()
+
+
+def _same_shape(what, p1, p2):
+	if p1.shape != p2.shape:
+		raise ValueError(f'find_amd.eval_metrics.{what}: shapes differ: {tuple(p1.shape)} / {tuple(p2.shape)}')
+
+
+def _psnr(mse):
+	return -10 * torch.log10(mse)
+
+
+def MSE(p1, p2):
+	"""nn.functional.mse_loss(p1, p2): mean of the squared differences over every element."""
+	_same_shape('MSE', p1, p2)
+	s = FN.image_metric_sums(p2.reshape(1, -1, 1), p1.reshape(1, -1, 1))
+	return (s[0, SQ] / p1.numel()).float()
+
+
+def PSNR(p1, p2):
+	"""-10 log10(MSE(p1, p2))."""
+	_same_shape('PSNR', p1, p2)
+	s = FN.image_metric_sums(p2.reshape(1, -1, 1), p1.reshape(1, -1, 1))
+	return _psnr(s[0, SQ] / p1.numel()).float()
+
+
+def _mse_masked64(p1, p2, mask):
+	_same_shape('MSE_masked', p1, p2)
+	if mask.shape == p1.shape[:-1]:   # a weight per pixel, counted once per channel
+		C = p1.shape[-1]
+		s = FN.image_metric_sums(p2.reshape(1, -1, C), p1.reshape(1, -1, C), weight=_f32(mask).reshape(1, -1))
+		return s[0, WSQ] / (C * s[0, W])
+	w = mask.expand_as(p1)            # any other shape broadcasts to the values (expand_as raises where the reference does)
+	s = FN.image_metric_sums(p2.reshape(1, -1, 1), p1.reshape(1, -1, 1), weight=_f32(w).reshape(1, -1))
+	return s[0, WSQ] / s[0, W]
+
+
+def MSE_masked(p1, p2, mask):
+	"""sum(mask * (p1 - p2)^2) / sum(mask expanded to p1): mask of p1.shape[:-1] (one value per pixel, C channels) or of p1's shape."""
+	return _mse_masked64(p1, p2, mask).float()
+
+
+def PSNR_masked(p1, p2, mask):
+	return _psnr(_mse_masked64(p1, p2, mask)).float()
+
+
+def IOU(s1, s2, reduce='mean'):
+	"""sum(s1 * s2) / sum(max(s1, s2)) per [H, W] slice (leading dimensions are batch dimensions), then the mean over the slices."""
+	if reduce != 'mean':
+		raise NotImplementedError(f'Reduction method `{reduce}` for IOU not implemented.')
+	_same_shape('IOU', s1, s2)
+	if s1.dim() < 2:
+		raise ValueError(f'find_amd.eval_metrics.IOU: masks are [(batch) x H x W], got {tuple(s1.shape)}')
+	n_pix = s1.shape[-2] * s1.shape[-1]
+	a, b = _f32(s1).reshape(-1, n_pix), _f32(s2).reshape(-1, n_pix)
+	s = FN.image_metric_sums(b.unsqueeze(-1), a.unsqueeze(-1), pred_mask=b, gt_mask=a)
+	return (s[:, INTER] / s[:, UNION]).mean().float()
+
+
+def eval_2d_metrics(pred_rdrs, gt_rdrs, batch_size=None):
+	"""The metrics of eval_2d.py:86-121 for renders of N feet x M views (FootRenderer output dicts; gt_rdrs rendered with return_mask,
+	mask_out_faces and return_mask_out_masks, pred_rdrs with return_mask).  A group is `batch_size` consecutive views of one foot (default:
+	all M), as one pass of the reference's inner loop.  Returns {'MSE', 'PSNR_A', 'PSNR_B', 'PSNR_C', 'IOU'}: float64 tensors of
+	N * (M // batch_size) values, foot-major.  MSE and the PSNRs are taken over the whole group, IOU is the mean of its per-image IoUs.
+	The prediction is read as if 1 / 0 had been written into its image / mask under the GT's mask-out map (eval_2d.py:92-94); the dicts
+	are left as they are."""
+	gi, pi, gm, pm = gt_rdrs['image'], pred_rdrs['image'], gt_rdrs['mask'], pred_rdrs['mask']
+	if gi.dim() != 5 or pi.shape != gi.shape:
+		raise ValueError(f'find_amd.eval_2d_metrics: images must be (feet, views, H, W, C) of one shape, got {tuple(pi.shape)} / {tuple(gi.shape)}')
+	N, M, H, Wd, C = gi.shape
+	bs = M if batch_size is None else int(batch_size)
+	if bs < 1 or M % bs:
+		raise ValueError(f'find_amd.eval_2d_metrics: {M} views do not split into groups of {bs}')
+	hide = None if gt_rdrs.get('nothing_hidden', False) else gt_rdrs.get('mask_out_masks')
+	n_img, n_pix = N * M, H * Wd
+	s = FN.image_metric_sums(pi.reshape(n_img, n_pix, C), gi.reshape(n_img, n_pix, C), pred_mask=pm.reshape(n_img, n_pix),
+							 gt_mask=gm.reshape(n_img, n_pix), hide=None if hide is None else hide.reshape(n_img, n_pix))
+	per = s.view(n_img // bs, bs, 7)
+	S = per.sum(1)
+	n = bs * n_pix * C
+	mse = S[:, SQ] / n
+	return {'MSE': mse, 'PSNR_A': _psnr(mse), 'PSNR_B': _psnr(S[:, SQ_EACH] / n), 'PSNR_C': _psnr(S[:, SQ_COMMON] / n),
+			'IOU': (per[..., INTER] / per[..., UNION]).mean(1)}

@@ -886,6 +886,49 @@ def image_mse(a, b, a_mask=None, b_mask=None):
 	return _ImageMSE.apply(a, a_mask, b, b_mask)
 
 
+# ----------------------------------------------------------------------------------------------- 2-D evaluation sums
+IMAGE_METRIC_NAMES = ('sq', 'sq_each', 'sq_common', 'inter', 'union', 'wsq', 'w')   # column order of image_metric_sums (find_hip.h FIND_IMAGE_METRIC_*)
+
+
+def image_metric_sums(pred, gt, pred_mask=None, gt_mask=None, hide=None, weight=None):
+	"""Per-image sums of the 2-D evaluation (find_image_metrics), (n_img, 7) float64, columns IMAGE_METRIC_NAMES.
+	pred, gt (n_img, *pixels, C) fp32; pred_mask, gt_mask, weight (n_img, *pixels) fp32 or None (= 1); hide (n_img, *pixels) bool / uint8 or
+	None: where set, pred counts as 1 and pred_mask as 0 (eval_2d.py:92-94), the tensors themselves are not changed.  No gradient, no host
+	synchronisation: runs on the current stream."""
+	if pred.shape != gt.shape:
+		raise ValueError(f'find_amd.image_metric_sums: pred {tuple(pred.shape)} and gt {tuple(gt.shape)} differ')
+	if pred.dim() < 2:
+		raise ValueError(f'find_amd.image_metric_sums: images are (n_img, *pixels, C), got {tuple(pred.shape)}')
+	pix_shape = pred.shape[:-1]
+	for name, t in (('pred_mask', pred_mask), ('gt_mask', gt_mask), ('hide', hide), ('weight', weight)):
+		if t is not None and t.shape != pix_shape:
+			raise ValueError(f'find_amd.image_metric_sums: {name} {tuple(t.shape)} must have the images\' shape without channels {tuple(pix_shape)}')
+	_require_gpu(pred, gt, pred_mask, gt_mask, weight, hide)
+	dev = pred.device
+	for name, t in (('gt', gt), ('pred_mask', pred_mask), ('gt_mask', gt_mask), ('hide', hide), ('weight', weight)):
+		if t is not None and t.device != dev:
+			raise ValueError(f'find_amd.image_metric_sums: {name} is on {t.device}, pred on {dev}')
+	if hide is not None:
+		if hide.dtype not in (torch.bool, torch.uint8):
+			raise ValueError(f'find_amd.image_metric_sums: hide must be bool or uint8, got {hide.dtype}')
+		hide = hide.contiguous().view(torch.uint8)
+	n_img, C = int(pred.shape[0]), int(pred.shape[-1])
+	n_pix = pred[0].numel() // C if n_img else 0
+	sums = torch.empty((n_img, 7), dtype=torch.float64, device=dev)
+	if n_img == 0 or n_pix == 0:
+		return sums.zero_()
+	L = _lib.lib()
+	nbytes = L.find_image_metrics_ws_bytes(n_img, n_pix)
+	if nbytes < 0:
+		raise ValueError(f'find_amd.image_metric_sums: unsupported sizes n_img={n_img}, n_pix={n_pix}')
+	ws = _ws(nbytes, dev)
+	# (contiguous copies held in locals until the launch is queued)
+	pred, gt, pred_mask, gt_mask, weight = (None if t is None else t.detach().contiguous() for t in (pred, gt, pred_mask, gt_mask, weight))
+	check(L.find_image_metrics(ptr(pred), ptr(gt), ptr(pred_mask), ptr(gt_mask), ptr(hide), ptr(weight), n_img, n_pix, C, ptr(sums), ptr(ws),
+							   ws.numel(), current_stream(dev)), 'find_image_metrics')
+	return sums
+
+
 class MeshTopology:
 	"""Static per-template tables for the smoothness kernels: unique undirected edges, vertex->incident-corner CSR and
 	vertex->neighbour CSR (host-built once, cached per faces tensor)."""

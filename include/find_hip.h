@@ -353,6 +353,33 @@ int find_image_mse_bwd(const float* a, const float* a_mask, const float* b, cons
 					   const float* g_loss, float* d_a, float* d_a_mask, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * 2-D evaluation sums in one pass (src/eval/eval_2d.py:92-121 with the metrics of src/eval/eval_metrics.py:4-40).  Per image i, with
+ *   p~ = 1 where hide[i,p] else pred,   m~ = 0 where hide[i,p] else pred_mask    (the in-place edit of eval_2d.py:92-94, not written back)
+ *   sums[i][FIND_IMAGE_METRIC_SQ]        = sum_p,c (g - p~)^2                         MSE, PSNR_A
+ *   sums[i][FIND_IMAGE_METRIC_SQ_EACH]   = sum_p,c (g [gm>0] - p~ [m~>0])^2           PSNR_B (each image inside its own silhouette)
+ *   sums[i][FIND_IMAGE_METRIC_SQ_COMMON] = sum_p,c [gm>0 and m~>0] (g - p~)^2         PSNR_C (inside both)
+ *   sums[i][FIND_IMAGE_METRIC_INTER]     = sum_p gm m~                                IOU intersection
+ *   sums[i][FIND_IMAGE_METRIC_UNION]     = sum_p max(gm, m~)                          IOU union
+ *   sums[i][FIND_IMAGE_METRIC_WSQ]       = sum_p,c w (g - p~)^2                       MSE_masked
+ *   sums[i][FIND_IMAGE_METRIC_W]         = sum_p w                                    MSE_masked denominator (times channels)
+ * pred, gt (n_img, n_pix, channels) fp32; pred_mask, gt_mask, weight (n_img, n_pix) fp32 or NULL (= 1); hide (n_img, n_pix) bytes (0 / non-zero:
+ * the renderer's bool mask_out_masks) or NULL (= nothing hidden).  sums (n_img, 7) fp64.  ws: find_image_metrics_ws_bytes(n_img, n_pix)
+ * (-1 for bad sizes).  Terms are formed in fp32, at most 4 pixels of them added in fp32, everything after that in fp64; the block split
+ * depends on (n_img, n_pix) only and every reduction runs in a fixed order: bit-identical from run to run.
+ * ---------------------------------------------------------------------------------------------- */
+#define FIND_IMAGE_METRIC_SQ 0
+#define FIND_IMAGE_METRIC_SQ_EACH 1
+#define FIND_IMAGE_METRIC_SQ_COMMON 2
+#define FIND_IMAGE_METRIC_INTER 3
+#define FIND_IMAGE_METRIC_UNION 4
+#define FIND_IMAGE_METRIC_WSQ 5
+#define FIND_IMAGE_METRIC_W 6
+#define FIND_IMAGE_METRIC_COUNT 7
+int64_t find_image_metrics_ws_bytes(int64_t n_img, int64_t n_pix);
+int find_image_metrics(const float* pred, const float* gt, const float* pred_mask, const float* gt_mask, const uint8_t* hide, const float* weight,
+					   int64_t n_img, int64_t n_pix, int64_t channels, double* sums, void* ws, int64_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Mesh smoothness: mesh_edge_loss(target 0) and mesh_laplacian_smoothing('cot').
  * Replaces pytorch3d.loss.mesh_edge_loss / mesh_laplacian_smoothing (call site src/model/losses.py:95-97).
  * Topology is shared by every mesh in the batch (one template) and static, so the host builds two CSR tables once:
