@@ -13,6 +13,10 @@ import torch
 from . import functional as FN
 from .losses import sample_points_from_meshes
 
+# template vertex ids of the six keypoints on the PCA foot model's mesh (reference src/cfg.yaml:11, read by eval_3d.py:137-138 and
+# eval_2d.py:155-156): eval_3d_metrics(..., template_kp_idxs=PCA_KEYPOINTS) for a PCAModel fitted to Foot3D scans
+PCA_KEYPOINTS = (1308, 1270, 1271, 1113, 1033, 489)
+
 
 def keypoint_error_mm(pred_verts, template_kp_idxs, gt_kps):
 	"""pred_verts (N,V,3) registered predictions, template_kp_idxs (K) vertex ids, gt_kps (N,K,3) -> scalar mm."""

@@ -23,7 +23,7 @@ def _marked_faces(textures):
 
 
 def eval_2d(model, dataset, image_size=128, nviews=1, batch_size=1, R=None, T=None, feet_per_call=16, return_per_image=False, device='cuda'):
-	"""model: a NeuralDisplacementField whose validation latent tables are indexed by the dataset's item index (batch['idx'], as
+	"""model: a NeuralDisplacementField or a PCAModel whose validation latent tables are indexed by the dataset's item index (batch['idx'], as
 	eval_2d.py:28-35 samples them); dataset: the validation Foot3DDataset.  Views: linspace_views(nviews, dist=0.3, elev_min=-90,
 	elev_max=90) unless R, T are given; groups of `batch_size` consecutive views (nviews // batch_size of them per foot, the loop bound of
 	eval_2d.py:86).  Feet are rendered `feet_per_call` at a time; the metrics are per image sums composed in float64, so the result does

@@ -544,6 +544,49 @@ def register_points(verts, disp, reg):
 	return _Register.apply(verts, disp, reg)
 
 
+# ----------------------------------------------------------------------------------------------- PCA foot model
+class _PCAOffsets(torch.autograd.Function):
+	"""offsets[n,v,c] = sum_b coefs[v,b,c] * shapevec[n,b]     (model.py:581).  coefs in the (V, B, 3) layout of pca_coefs."""
+
+	@staticmethod
+	def forward(ctx, coefs, shapevec):
+		_require_gpu(coefs, shapevec)
+		if coefs.requires_grad:
+			raise RuntimeError('find_amd.pca_offsets: pca_coefs is frozen in FIND (requires_grad=False, model.py:648); only shapevec gets a gradient')
+		if coefs.dim() != 3 or coefs.shape[2] != 3 or shapevec.dim() != 2 or shapevec.shape[1] != coefs.shape[1]:
+			raise RuntimeError(f'find_amd.pca_offsets: bad shapes coefs {tuple(coefs.shape)} (want (V, B, 3)) shapevec {tuple(shapevec.shape)} (want (N, B))')
+		if coefs.device != shapevec.device:
+			raise RuntimeError(f'find_amd.pca_offsets: coefs on {coefs.device}, shapevec on {shapevec.device}')
+		L = _lib.lib()
+		coefs, shapevec = _c(coefs), _c(shapevec)
+		V, B, _ = coefs.shape
+		N = shapevec.shape[0]
+		out = torch.empty(N, V, 3, dtype=torch.float32, device=coefs.device)
+		if N == 0:
+			return out
+		check(L.find_pca_fwd(ptr(coefs), V, B, ptr(shapevec), N, ptr(out), current_stream(coefs.device)), 'find_pca_fwd')
+		ctx.save_for_backward(coefs)
+		return out
+
+	@staticmethod
+	def backward(ctx, g):
+		L = _lib.lib()
+		coefs, = ctx.saved_tensors
+		V, B, _ = coefs.shape
+		g = _c(g)
+		N = g.shape[0]
+		d_shapevec = torch.empty(N, B, dtype=torch.float32, device=g.device)
+		ws = _ws(L.find_pca_bwd_ws_bytes(N, V, B), g.device)
+		check(L.find_pca_bwd(ptr(coefs), V, B, ptr(g), N, ptr(d_shapevec), ptr(ws), ws.numel(), current_stream(g.device)), 'find_pca_bwd')
+		return None, d_shapevec
+
+
+def pca_offsets(coefs, shapevec):
+	"""Per-vertex offsets (N, V, 3) of the linear PCA model from its coefficients (V, B, 3) and shape codes (N, B); HIP forward and
+	backward (find_pca_fwd / find_pca_bwd), gradient to shapevec only."""
+	return _PCAOffsets.apply(coefs, shapevec)
+
+
 # ----------------------------------------------------------------------------------------------- surface sampling
 def _faces_i32(faces):
 	f = faces if faces.dtype == torch.int32 else faces.to(torch.int32)

@@ -526,3 +526,112 @@ class NeuralDisplacementField(Model):
 		out = super().to(device)
 		self._rebuild_template_mesh()
 		return out
+
+
+class PCAModel(Model):
+	"""Linear PCA foot model, the baseline FIND is compared with (reference model.py:536-655): template + sum_b coefs[:, b] * shapevec[b],
+	then the learned similarity registration.  Offsets run in find_pca_fwd / find_pca_bwd, registration in find_register_fwd / bwd (the
+	kernels of NeuralDisplacementField.get_meshes).  The model comes from a .mat file (load_from_mat) or a .pth checkpoint (load); state_dict
+	keys are the reference's (template_verts, template_faces, pca_var, pca_coefs, reg.data, reg_val.data, shapevec.data, shapevec_val.data),
+	so checkpoints move between the two in both directions."""
+
+	def __init__(self, *args, train_size=None, val_size=None, device='cuda', **kwargs):
+		super().__init__()
+		self.params = dict(train_size=train_size, val_size=val_size)
+		self.train_size, self.val_size = train_size, val_size
+		# set by configure_template
+		self.template_verts = self.template_faces = self.template_mesh = None
+		self.pca_var = None     # (B,) as stored in the .mat file; never read (as upstream)
+		self.pca_coefs = None   # (V, B, 3)
+		self.latent_vectors_train, self.latent_vectors_val = [], []
+		self.shapevec, self.shapevec_val = None, None
+		ident = np.array([0] * 6 + [1] * 3)
+		self.reg = LatentVector(train_size, vec_size=9, name='reg_train', device=device, init_values=ident)
+		self.reg_val = LatentVector(val_size, vec_size=9, name='reg_val', device=device, init_values=ident)
+		self.latent_vectors_train.append(self.reg)
+		self.latent_vectors_val.append(self.reg_val)
+		self.configure_params()
+
+	def configure_params(self):
+		"""Parameter groups read by train.py:161-168 (model.py:563-567)."""
+		self.main_params = make_params_list(self.shapevec)
+		self.val_params = make_params_list(self.shapevec_val)
+		self.reg_params = make_params_list(self.reg, self.reg_val)
+		self.latent_params = make_params_list(self.shapevec, self.shapevec_val)
+
+	def _rebuild_template_mesh(self):
+		if self.template_verts is not None:
+			self.template_mesh = Meshes(verts=self.template_verts.data, faces=self.template_faces.data[0])
+
+	def _apply(self, fn, *args, **kwargs):
+		out = super()._apply(fn, *args, **kwargs)
+		self._rebuild_template_mesh()
+		return out
+
+	def get_meshes(self, shapevec=None, reg=None, **kwargs):
+		"""dict(meshes, offsets, verts) for shape codes (N, B) and registrations (N, 9) or None (model.py:573-601).  Every other keyword --
+		no_displacement, lazy_colours, ... -- is accepted and ignored, as upstream.  The texture is a constant grey."""
+		N = shapevec.shape[0]
+		meshes = extend_template(self.template_mesh, N=N)
+		tv = self.template_verts.data   # (1, V, 3), shared by the N feet
+		offsets = FN.pca_offsets(self.pca_coefs, shapevec)
+		X = FN.register_points(tv, offsets, reg) if reg is not None else tv + offsets
+		meshes = meshes.update_padded(X)
+		meshes.textures = TexturesVertex(torch.full(X.shape, 0.5, dtype=torch.float32, device=X.device))
+		return dict(meshes=meshes, offsets=offsets, verts=X)
+
+	def get_meshes_from_batch(self, batch, is_train=True, **kwargs):
+		sfx = 'train' if is_train else 'val'
+		return self.get_meshes(shapevec=batch.get(f'shapevec_{sfx}', None), reg=batch.get(f'reg_{sfx}', None))
+
+	def forward(self, *args, **kwargs):
+		raise NotImplementedError('PCAModel has no field to query: it is evaluated through get_meshes / get_meshes_from_batch (the texture loss, '
+								  'which queries a colour field, does not apply to it)')
+
+	@classmethod
+	def load_from_mat(cls, src, device, **kwargs):
+		"""pcaMean (3V) -> template_verts (1, V, 3); mesh (F, 3), 1-based -> template_faces (1, F, 3); pcaCoefs (3V, B), rows vertex-major ->
+		pca_coefs (V, B, 3); pcaVar -> pca_var as stored (model.py:610-628)."""
+		from scipy.io import loadmat
+		data = loadmat(src)
+		sd = {}
+		sd['template_verts'] = torch.from_numpy(data['pcaMean'].reshape(-1, 3)).unsqueeze(0).float()
+		sd['template_faces'] = torch.from_numpy(data['mesh']).unsqueeze(0).long() - 1
+		V = sd['template_verts'].shape[1]
+		sd['pca_coefs'] = torch.from_numpy(data['pcaCoefs']).reshape(V, 3, -1).permute(0, 2, 1).float()
+		sd['pca_var'] = torch.from_numpy(data['pcaVar']).float()
+		model = cls(device=device, **kwargs)
+		model.configure_template(sd, device=device)
+		model.load_state_dict(sd, strict=False)
+		model.configure_params()
+		return model
+
+	@classmethod
+	def load(cls, file, device='cuda', opts=None, **kwargs):
+		if file.endswith('.pth'):
+			model = super().load(file, device=device, opts=opts, **kwargs)
+			# Deviation from upstream: Model.load never calls configure_params again, so there the four groups stay empty after a .pth
+			# load (torch.optim raises on them).  They are filled here, on both paths (DESIGN 2).
+			model.configure_params()
+			return model
+		if file.endswith('.mat'):
+			return cls.load_from_mat(file, device=device, opts=opts, **kwargs)
+		raise NotImplementedError(f'Filetype `{os.path.splitext(file)[-1]}` for PCA model not understood')
+
+	def configure_template(self, state_dict, device='cuda'):
+		"""Template, coefficients and the shape-code tables, B wide, appended after reg (model.py:639-655)."""
+		self.template_verts = nn.Parameter(state_dict['template_verts'].float().to(device), requires_grad=False)
+		self.template_faces = nn.Parameter(state_dict['template_faces'].to(device), requires_grad=False)
+		self._rebuild_template_mesh()
+		self.pca_var = nn.Parameter(state_dict['pca_var'].to(device), requires_grad=False)
+		self.pca_coefs = nn.Parameter(state_dict['pca_coefs'].float().to(device), requires_grad=False)
+		V, B, _ = self.pca_coefs.shape
+		self.shapevec = LatentVector(self.train_size, vec_size=B, name='shapevec_train', device=device)
+		self.shapevec_val = LatentVector(self.val_size, vec_size=B, name='shapevec_val', device=device)
+		self.latent_vectors_train.append(self.shapevec)
+		self.latent_vectors_val.append(self.shapevec_val)
+
+	def to(self, device):
+		out = super().to(device)
+		self._rebuild_template_mesh()
+		return out

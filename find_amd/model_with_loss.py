@@ -14,12 +14,12 @@ import torch
 from . import functional as FN
 from . import losses as _losses
 from .losses import DisplacementLoss, MeshSmoothnessLoss, SilhouetteLoss, TextureLossGTSpace
-from .model import NeuralDisplacementField
+from .model import NeuralDisplacementField, PCAModel
 from .renderer import FootRenderer
 
 nn = torch.nn
 
-model_zoo = dict(neural=NeuralDisplacementField)
+model_zoo = dict(neural=NeuralDisplacementField, pca=PCAModel)
 
 OUT_OF_SCOPE_FLAGS = {
 	'vgg_perc': 'perceptual / restyle / contrastive losses are out of scope (SURVEY.md §2 #4)',
@@ -130,8 +130,8 @@ def _third_stream(device):
 def model_class_from_opts(opts):
 	kind = getattr(opts, 'model_type', 'neural')
 	if kind not in model_zoo:
-		raise NotImplementedError(f"model_type '{kind}': only the neural displacement field is on the hot path (PCA / SUPR / "
-								  'vertex-feature baselines are out of scope, SURVEY.md §2 #7-9)')
+		raise NotImplementedError(f"model_type '{kind}': only the neural displacement field and the PCA baseline are on the hot path (the SUPR "
+								  'and vertex-feature baselines are out of scope, SURVEY.md §2 #7-9)')
 	return model_zoo[kind]
 
 
@@ -254,6 +254,10 @@ class ModelWithLoss(nn.Module):
 		for name, why in OUT_OF_SCOPE_FLAGS.items():
 			if given[name]:
 				raise NotImplementedError(why)
+		if texture and isinstance(self.model, PCAModel):
+			# (upstream ends in an AttributeError inside TextureLossGTSpace, losses.py:22-57)
+			raise NotImplementedError('texture=True: the texture loss queries the model\'s colour field, and the PCA model (model_type=\'pca\') has '
+									  'none; switch the texture term off for it')
 		enabled = dict(chamf=chamf, smooth=smooth, texture=texture, pix=pix, sil=sil)
 
 		st = _Step()

@@ -274,6 +274,20 @@ int find_register_bwd(const float* verts, int64_t verts_batch, const float* disp
 					  void* ws, int64_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Linear PCA foot model: offsets[n,v,c] = sum_b coefs[v,b,c] * shapevec[n,b]   (PCAModel.get_meshes, src/model/model.py:581;
+ * the registration that follows is find_register_fwd with disp = offsets, model.py:584-594).
+ * coefs (V, B, 3) fp32 in the state_dict layout of pca_coefs; shapevec (n_feet, B); offsets (n_feet, V, 3).  1 <= B <= 4000,
+ * 1 <= V < 2^29, 1 <= n_feet <= 2^20.  coefs is read once per call for all feet.
+ * ---------------------------------------------------------------------------------------------- */
+int find_pca_fwd(const float* coefs, int64_t V, int64_t B, const float* shapevec, int64_t n_feet, float* offsets, void* stream);
+/* d_offsets (n_feet, V, 3) -> d_shapevec[n,b] = sum_{v,c} d_offsets[n,v,c] * coefs[v,b,c]  (n_feet, B); pca_coefs is frozen
+ * (requires_grad=False, model.py:648) and gets no gradient.  ws: find_pca_bwd_ws_bytes() (-1 for bad sizes): one partial row per vertex
+ * tile, added in tile order by a second kernel -- no atomics, bit-identical from run to run. */
+int64_t find_pca_bwd_ws_bytes(int64_t n_feet, int64_t V, int64_t B);
+int find_pca_bwd(const float* coefs, int64_t V, int64_t B, const float* d_offsets, int64_t n_feet, float* d_shapevec, void* ws, int64_t ws_bytes,
+				 void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Surface sampling gather.  Replaces the gather/lerp half of pytorch3d.ops.sample_points_from_meshes
  * (call sites src/model/losses.py:39-41,63,67; src/eval/eval_3d.py:149-150); the random draws
  * (face index, u, v) are INPUTS so CPU and GPU runs see identical samples.
