@@ -48,6 +48,10 @@ class RenderParams(Structure):
 	]
 
 
+class PointsParams(Structure):
+	_fields_ = [('image_h', c_int32), ('image_w', c_int32), ('fov_deg', c_float), ('radius', c_float), ('points_per_pixel', c_int32)]
+
+
 # name -> (restype, argtypes); mirrors include/find_hip.h one to one
 _P = c_void_p
 _I = c_int64
@@ -114,6 +118,7 @@ PROTOTYPES = {
 	'find_render_fwd': (c_int, [POINTER(RenderParams), _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P]),
 	'find_render_bwd': (c_int, [POINTER(RenderParams), _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P]),
 	'find_render_flags': (c_int, [_P, _P, _P]),
+	'find_points_render': (c_int, [POINTER(PointsParams), _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
 }
 # include/find_hip_diag.h: what libfind_hip_diag.so exports on top
 DIAG_PROTOTYPES = {

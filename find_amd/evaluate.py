@@ -1,13 +1,19 @@
 """The metric loop of reference src/eval/eval_2d.py (main, eval_2d.py:50-121) on the HIP path: every validation foot and its prediction
 rendered from the same views, PSNR_A / _B / _C, MSE and IOU per group of views (eval_metrics.eval_2d_metrics), the mean over all groups of
 all feet.  The HD three-view render, the PNG writes, the results table and the experiment-directory walk (run_on_exp) are visualisation
-and out of scope."""
+and out of scope.
+
+eval_3d is the loop of reference src/eval/eval_3d.py (main, eval_3d.py:56-225) the same way: keypoint error, Chamfer and its z cut-off
+variant (eval_metrics.eval_3d_metrics) over every validation foot, and optionally the per-foot keypoint table behind errors.png and the
+top-down keypoint renders of render_correspondences (eval_3d.py:94-99).  PNG / mp4 / OBJ writes, spins, per-vertex error textures and the
+matplotlib table are out of scope."""
 import torch
 from torch.utils.data import DataLoader
 
 from .dataset import BatchCollator
-from .eval_metrics import eval_2d_metrics
+from .eval_metrics import eval_2d_metrics, eval_3d_metrics
 from .renderer import FootRenderer
+from .structures import Meshes
 
 METRICS = ('MSE', 'PSNR_A', 'PSNR_B', 'PSNR_C', 'IOU')
 
@@ -56,3 +62,60 @@ def eval_2d(model, dataset, image_size=128, nviews=1, batch_size=1, R=None, T=No
 	per = {k: torch.cat(v) for k, v in per.items()}
 	out = {k: float(v.mean()) for k, v in per.items()}
 	return (out, per) if return_per_image else out
+
+
+def eval_3d(model, dataset, template_kp_idxs, samples=10000, z_cutoff=0.07, feet_per_call=16, render_correspondences=False, image_size=256,
+			return_per_foot=False, device='cuda'):
+	"""model: a NeuralDisplacementField or a PCAModel whose validation latent tables are indexed by the dataset's item index (batch['idx']);
+	dataset: the validation Foot3DDataset, every foot with keypoints; template_kp_idxs: the template vertices of the keypoints (the
+	template foot's kp_idxs for a neural model, eval_metrics.PCA_KEYPOINTS for a PCAModel; eval_3d.py:132-138).  Ground-truth keypoints
+	are the scan's vertices at its kp_idxs, predicted ones the prediction's vertices at template_kp_idxs.  Predictions are made
+	`feet_per_call` at a time; the metrics are taken once over all feet, as eval_3d.py:146-161 does, so the keypoint table does not depend
+	on that choice and the Chamfer terms draw their samples as one eval_3d_metrics call over all feet would.
+	Returns {'Keypoint (mm)', 'Chamf z-cutoff <z> (μm)', 'Chamf (μm)'} as floats; with return_per_foot or render_correspondences a second
+	dict follows, holding 'keypoint_mm' (N,K) float32 (the data of errors.png) and / or 'gt' and 'pred', the keypoint_blend images
+	(N,1,H,W,3) from view_from('topdown').  A foot without keypoints raises ValueError (upstream reads vertex 0 for it)."""
+	collate = BatchCollator(device=device).collate_batches
+	loader = DataLoader(dataset, batch_size=feet_per_call, shuffle=False, collate_fn=collate)
+	kp_t = torch.as_tensor(template_kp_idxs, dtype=torch.long, device=device)
+	renderer = FootRenderer(image_size=image_size, device=device) if render_correspondences else None
+	R, T = renderer.view_from('topdown') if render_correspondences else (None, None)
+	gt_v, gt_f, pred_v, pred_f, gt_kps, pred_verts, images = [], [], [], [], [], [], {'gt': [], 'pred': []}
+	was_training = model.training
+	model.eval()
+	try:
+		with torch.no_grad():
+			for batch in loader:
+				has = [bool(h) for h in batch['has_keypoints']]
+				if not all(has):
+					raise ValueError(f'find_amd.evaluate.eval_3d: foot {batch["name"][has.index(False)]} has no keypoints')
+				idx = batch['idx'].to(device)
+				batch.update({vec.name: vec[idx] for vec in model.latent_vectors_val})
+				res = model.get_meshes_from_batch(batch, is_train=False)
+				gt = batch['mesh']
+				kp_idxs = torch.as_tensor(batch['kp_idxs'], device=device).long()
+				gkp = torch.stack([v[k] for v, k in zip(gt.verts_list(), kp_idxs)])
+				pkp = res['verts'][:, kp_t]
+				gt_v += gt.verts_list(); gt_f += gt.faces_list()
+				pred_v += res['meshes'].verts_list(); pred_f += res['meshes'].faces_list()
+				gt_kps.append(gkp)
+				pred_verts.append(res['verts'])
+				if render_correspondences:
+					images['gt'].append(renderer(gt, R, T, return_images=True, keypoints=gkp, keypoints_blend=True)['keypoints_blend'])
+					images['pred'].append(renderer(res['meshes'], R, T, return_images=True, keypoints=pkp, keypoints_blend=True)['keypoints_blend'])
+			gt_kps = torch.cat(gt_kps)
+			pred_verts = torch.cat(pred_verts)
+			metrics = eval_3d_metrics(Meshes(pred_v, pred_f), Meshes(gt_v, gt_f), pred_verts=pred_verts, template_kp_idxs=kp_t, gt_kps=gt_kps,
+									  samples=samples, z_cutoff=z_cutoff)
+			per_foot = torch.norm(pred_verts[:, kp_t] - gt_kps, dim=-1) * 1e3
+	finally:
+		model.train(was_training)
+	out = {k: float(metrics[k]) for k in ('Keypoint (mm)', f'Chamf z-cutoff {z_cutoff} (μm)', 'Chamf (μm)')}
+	if not (return_per_foot or render_correspondences):
+		return out
+	extra = {}
+	if return_per_foot:
+		extra['keypoint_mm'] = per_foot
+	if render_correspondences:
+		extra.update({k: torch.cat(v) for k, v in images.items()})
+	return out, extra

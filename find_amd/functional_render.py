@@ -1,4 +1,5 @@
-"""torch.autograd binding of the HIP renderer (find_render_fwd / find_render_bwd).  GPU only, no fallback."""
+"""torch.autograd binding of the HIP renderer (find_render_fwd / find_render_bwd) and the keypoint splat render (find_points_render,
+forward only).  GPU only, no fallback."""
 import atexit
 import contextlib
 import ctypes
@@ -9,7 +10,7 @@ import warnings
 import torch
 
 from . import _lib
-from ._lib import RenderParams, check, current_stream, ptr
+from ._lib import PointsParams, RenderParams, check, current_stream, ptr
 from .functional import _c, _faces_i32, _require_gpu, _ws
 
 
@@ -288,3 +289,40 @@ def render_uv(verts, tex, faces, R, T, params, want_mask=True, want_frags=False)
 		texel = uv_sample(tex.maps_padded(), tex.verts_uvs_padded(), tex.faces_uvs_padded(), fl.reshape(N, M * H * W), bary.reshape(N, M * H * W, 3))
 		image = o0 + (o1 - o0) * texel.reshape(N, M, H, W, 3)
 	return mask, image, (p2f if want_frags else None), (zbuf if want_frags else None)
+
+
+def render_points(points, features, R, T, image_size, radius=0.03, points_per_pixel=10, fov_deg=60.0, return_fragments=False):
+	"""PyTorch3D's PointsRasterizer + PointsRenderer(AlphaCompositor()) as FootRenderer draws keypoints (renderer.py:139-142, 365-376):
+	points, features (N,P,3) world space, R (M,3,3), T (M,3)  ->  image (N,M,H,W,3), cloud n drawn in each of the M views, 0 where no
+	point lands.  A point covers a pixel if its NDC distance is below `radius`; each pixel composites its `points_per_pixel` (1 .. 32)
+	nearest points in view-space z front to back with weight 1 - d^2 / radius^2.  return_fragments: also (idx (N,M,H,W,K) int32 point
+	index within the cloud, zbuf (view-space z), dists (d^2)), -1 in empty slots.  Forward only: nothing in FIND trains through this
+	render, and it raises if a gradient would be needed."""
+	if torch.is_grad_enabled() and (points.requires_grad or features.requires_grad):
+		raise RuntimeError('find_amd.render_points: the point render has no backward; call it under torch.no_grad() or on detached tensors')
+	_require_gpu(points, features, R, T)
+	if points.dim() != 3 or points.shape[-1] != 3 or features.shape != points.shape:
+		raise ValueError(f'find_amd.render_points: points and features must both be (N,P,3), got {tuple(points.shape)} / {tuple(features.shape)}')
+	if R.dim() != 3 or R.shape[1:] != (3, 3) or T.shape != (R.shape[0], 3):
+		raise ValueError(f'find_amd.render_points: R (M,3,3) and T (M,3) expected, got {tuple(R.shape)} / {tuple(T.shape)}')
+	p = PointsParams()
+	if isinstance(image_size, (tuple, list)):
+		p.image_h, p.image_w = int(image_size[0]), int(image_size[1])
+	else:
+		p.image_h = p.image_w = int(image_size)
+	p.fov_deg, p.radius, p.points_per_pixel = fov_deg, radius, int(points_per_pixel)
+	points, features = _c(points.detach()), _c(features.detach())
+	R, T = _c(R.detach().to(points.device)), _c(T.detach().to(points.device))
+	N, P, _ = points.shape
+	M = R.shape[0]
+	H, W, K = p.image_h, p.image_w, p.points_per_pixel
+	dev = points.device
+	image = torch.empty(N, M, H, W, 3, device=dev)
+	frags = None
+	if return_fragments:
+		shape = (N, M, H, W, max(K, 1))
+		frags = (torch.empty(shape, device=dev, dtype=torch.int32), torch.empty(shape, device=dev), torch.empty(shape, device=dev))
+	idx, zbuf, dists = frags if frags is not None else (None, None, None)
+	check(_lib.lib().find_points_render(ctypes.byref(p), ptr(points), ptr(features), ptr(R), ptr(T), N, M, P, ptr(image), ptr(idx), ptr(zbuf),
+										ptr(dists), current_stream(dev)), 'find_points_render')
+	return (image, frags) if return_fragments else image

@@ -1,6 +1,7 @@
 """FootRenderer on the MI355X hot path: host-side mirror of reference src/model/renderer.py (same class name, constructor
 keywords, view helpers and forward() keywords / outputs); all rendering arithmetic runs in libfind_hip.so
-(find_amd.functional_render).  Keypoint splatting and the N-channel feature shader are out of scope."""
+(find_amd.functional_render).  Keypoints are drawn as PyTorch3D's point renderer draws them (functional_render.render_points, one HIP
+kernel); the N-channel feature shader is out of scope."""
 from typing import Union
 
 import numpy as np
@@ -26,6 +27,8 @@ class FootRenderer(nn.Module):
 		self.background_color = tuple(float(c) for c in background_color)
 		self.bin_size, self.max_faces_per_bin = bin_size, max_faces_per_bin
 		self.light_location = (0., 0., 100.)  # PointLights(location=[[0, 0, 100]])  (renderer.py:114)
+		# PointsRasterizationSettings(image_size, radius=0.03, points_per_pixel=10) + AlphaCompositor() (renderer.py:139-142)
+		self.points_radius, self.points_per_pixel = 0.03, 10
 		self.params = FR.make_params(image_size, faces_per_pixel=100, background=self.background_color, light_pos=self.light_location,
 									 znear=0.02, z_clip=z_clip_value, clip_faces=clip_faces)
 
@@ -79,9 +82,17 @@ class FootRenderer(nn.Module):
 				mask_out_faces=False, masked_faces=None, keypoints=None, keypoints_blend=False, lights=None, return_mask_out_masks=False,
 				return_features=False, features=None) -> dict:
 		"""Render N meshes from M views: image [N,M,H,W,3], mask [N,M,H,W] (soft silhouette when mask_with_grad), optional
-		depth and mask-out masks (reference renderer.py:247-383).  Image index = mesh*M + view."""
-		if keypoints is not None or keypoints_blend:
-			raise NotImplementedError('keypoint splatting (points renderer) is visualisation-only and out of scope')
+		depth and mask-out masks (reference renderer.py:247-383).  Image index = mesh*M + view.
+		keypoints (N,P,3): out['keypoints'] (N,M,H,W,3), the points drawn red by PyTorch3D's point renderer (functional_render.render_points;
+		no depth test against the mesh, no gradient) -- mesh n's keypoints in each of its M views, as renderer.py:367 meant (upstream's own
+		line discards that expansion and works for M = 1 only); with keypoints_blend also out['keypoints_blend'], the image with the
+		splats over it (~any(pcl > 0) * image + any(pcl > 0) * pcl), which needs return_images.  keypoints_blend without keypoints is
+		ignored, as upstream."""
+		if keypoints is not None:
+			if keypoints_blend and not return_images:   # (a NameError upstream)
+				raise ValueError('FootRenderer: keypoints_blend draws the keypoints over the image: it needs return_images=True')
+			if keypoints.dim() != 3 or keypoints.shape[-1] != 3 or keypoints.shape[0] != len(input_meshes):
+				raise ValueError(f'FootRenderer: keypoints must be (N,P,3) with N = {len(input_meshes)} meshes, got {tuple(keypoints.shape)}')
 		if return_features or features is not None:
 			raise NotImplementedError('per-vertex feature rendering needs the restyle encoder and is out of scope')
 		if lights is not None:
@@ -105,7 +116,7 @@ class FootRenderer(nn.Module):
 		# (pix_to_face is read below only to hide faces: when the caller names some, or for UV textures' (0,0)-UV convention)
 		want_frags = (mask_out_faces and (masked_faces is not None or uv_tex)) or return_depth
 		if not (return_images or want_soft or want_frags):
-			return dict()
+			return self._keypoints(dict(), None, keypoints, keypoints_blend, R, T, dev)
 		if return_images and uv_tex:
 			# GT scans (dataset.py:263-271): no gradient flows to a UV-textured mesh anywhere in the reference
 			if verts.requires_grad:
@@ -145,6 +156,7 @@ class FootRenderer(nn.Module):
 			if return_mask:
 				mask = torch.where(mask_out, torch.zeros_like(mask), mask)
 
+		self._keypoints(out, renders, keypoints, keypoints_blend, R, T, dev)
 		if return_images:
 			out['image'] = renders
 		if return_mask:
@@ -152,4 +164,19 @@ class FootRenderer(nn.Module):
 		if return_mask_out_masks:
 			out['mask_out_masks'] = mask_out
 			out['nothing_hidden'] = nothing_hidden
+		return out
+
+	def _keypoints(self, out, renders, keypoints, keypoints_blend, R, T, dev):
+		"""out['keypoints'] (and out['keypoints_blend'] over `renders`) as renderer.py:365-376 forms them."""
+		if keypoints is None:
+			return out
+		kp = keypoints.to(dev).float()
+		features = torch.zeros_like(kp)
+		features[..., 0] = 1
+		pcl = FR.render_points(kp, features, R, T, (self.params.image_h, self.params.image_w), radius=self.points_radius,
+							   points_per_pixel=self.points_per_pixel, fov_deg=self.params.fov_deg)
+		out['keypoints'] = pcl
+		if keypoints_blend:
+			pcl_mask = torch.any(pcl > 0, dim=-1).unsqueeze(-1)
+			out['keypoints_blend'] = ~pcl_mask * renders + pcl_mask * pcl
 		return out

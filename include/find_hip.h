@@ -480,6 +480,27 @@ int find_render_bwd(const find_render_params* rp, const float* verts, const int3
  * only a pixel with more than 4096 candidates is not resolved -- all of its candidates stay blended. */
 int find_render_flags(const void* ws, int32_t* out2, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Keypoint splats (FootRenderer(..., keypoints=...), src/model/renderer.py:139-142, 365-376): PyTorch3D's PointsRasterizer with
+ * PointsRasterizationSettings(radius, points_per_pixel) and the renderer's FoVPerspectiveCameras, fused with PointsRenderer +
+ * AlphaCompositor (no background), forward only.  Image index = cloud*n_views + view: cloud n is drawn in each of the n_views views.
+ * A point with view-space z < 0 is skipped; it covers a pixel if d^2 < radius^2 in NDC (strict); each pixel keeps the
+ * points_per_pixel points of smallest z (equal z: lower point index) and composites them front to back with w = 1 - d^2 / radius^2.
+ * points, features (n_clouds,P,3); R (n_views,3,3), T (n_views,3) as find_render_fwd.  Outputs (any may be NULL, not all):
+ * image (n_clouds*n_views,H,W,3), 0 where no point lands; idx (…,H,W,K) int32 point index within the cloud, zbuf (view-space z) and
+ * dists (d^2) (…,H,W,K), -1 in empty slots.  1 <= points_per_pixel <= 32, radius > 0.  No workspace, no host synchronisation, no
+ * atomics: repeated calls are bit-identical.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct find_points_params {
+	int32_t image_h, image_w;
+	float fov_deg;           /* 60, as find_render_params */
+	float radius;            /* 0.03 NDC units (renderer.py:140) */
+	int32_t points_per_pixel;/* 10 (renderer.py:140) */
+} find_points_params;
+
+int find_points_render(const find_points_params* pp, const float* points, const float* features, const float* R, const float* T,
+					   int64_t n_clouds, int64_t n_views, int64_t P, float* image, int32_t* idx, float* zbuf, float* dists, void* stream);
+
 
 /* ------------------------------------------------------------------------------------------------
  * UV textures.  Replaces pytorch3d TexturesUV.sample_textures as the reference uses it for GT scans
