@@ -13,7 +13,11 @@ in that configuration, so views := 1.  Per GPU: 16 feet x 6890-
 scaling: every rank owns 16 distinct feet; the gradients of the replicated parameters are averaged with ONE RCCL all-reduce per
 step (find_amd/distributed.py).  Rank 0 prints ONE JSON line.
 
-Objects on that line:
+A plain run does what the headline figure needs and nothing else: set up, prime, W warm-up + K timed steps (x --repeats), the
+--dump-outputs arrays when asked, the line.  Everything else it can measure or check comes with --full:
+
+Objects on the --full line (and, in full, in bench_records.json):
+  collective   -- (N > 1) what the gradient exchange saw: backend, world size, the ranks' devices, bucket bytes, all-reduce time.
   roofline     -- the step's dominant kernel (256x256 Linear+ReLU fp32-MFMA GEMM over all 110 240 head rows) timed live with HIP
                   events on the launch stream; achieved = 2*rows*256*256 flop / average duration.
   cpu_baseline -- the oracle's composition of the same step (oracle/mlp_ref.py + oracle/geom_ref.py) on a bounded sample, rank 0, N=1.
@@ -1136,12 +1140,15 @@ def main():
 	ap.add_argument('--gpus', type=int, default=1)
 	ap.add_argument('--steps', type=int, default=30)
 	ap.add_argument('--warmup', type=int, default=5)
+	ap.add_argument('--full', action='store_true', help='headline: besides the headline figure, everything else the benchmark measures -- the roofline '
+					'loops of the dominant kernels, the CPU baseline, the collective block (N > 1), the records of the other configurations (N = 1) -- '
+					'on the line and in full in bench_records.json.  Without it the run sets up, times, dumps (--dump-outputs) and prints the line')
 	ap.add_argument('--no-cpu-baseline', action='store_true')
 	ap.add_argument('--repeats', type=int, default=5, help='repetitions of the headline K-step timing; the median is reported, all are listed (5: a host that hiccups during two of three repetitions moved a 1.53-ms step to 1.71)')
 	ap.add_argument('--no-prime', action='store_true', help='no untimed priming phase before the warm-up steps (Run.timed): measures a cold GPU')
-	ap.add_argument('--headline-only', action='store_true', help='only the timed headline loop (no records, no CPU leg, no isolated kernel loop): the command to put under rocprofv3')
+	ap.add_argument('--headline-only', action='store_true', help='only the timed headline loop (no records, no CPU leg, no isolated kernel loop), even with --full: the command to put under rocprofv3')
 	ap.add_argument('--no-graph', action='store_true', help='skip the HIP-graph variant of the batch-1 record')
-	ap.add_argument('--no-records', action='store_true', help='skip the nested records of the other configurations')
+	ap.add_argument('--no-records', action='store_true', help='with --full: skip the nested records of the other configurations')
 	ap.add_argument('--train3d', action='store_true', help='(default) the headline line: the reference training configuration')
 	ap.add_argument('--train3d-b1', action='store_true', help='instead of the headline line: only the batch-1 train_3d records')
 	ap.add_argument('--b1-only', default='', help='with --train3d-b1: comma-separated record names to run (diagnosis)')
@@ -1169,6 +1176,7 @@ def main():
 	if args.no_prime:
 		Run.PRIME_S = 0.0
 	with_cpu = not args.no_cpu_baseline and not args.headline_only
+	extras = args.full and not args.headline_only   # the headline's measurements beyond its own figure
 	if args.subpaths:
 		return subpaths(with_cpu)
 	run = Run(args.gpus)
@@ -1212,8 +1220,8 @@ def main():
 	ms = sorted(ms_all)[(len(ms_all) - 1) // 2]
 	if args.dump_outputs and run.rank == 0:
 		dump_outputs(args.dump_outputs, su)
-	coll = su['collective']() if run.world > 1 else None
-	full = {}   # everything that does not fit the line: RECORDS_FILE
+	coll = su['collective']() if run.world > 1 and extras else None
+	full = {}   # everything that does not fit the line: RECORDS_FILE (--full)
 	if run.rank == 0:
 		fl = train3d_executed_flops(N_FEET)
 		cfg = {'workload': short(f'train_3d.yaml network-stage step: {N_FEET} feet x {N_VERTS}-vertex template per GPU, {N_GT_VERTS}-vertex GT scans, '
@@ -1233,7 +1241,7 @@ def main():
 								'src/train/opts.py:40 batch_size_train=1 -> records.train3d_b1; 16 feet per GPU is the data-parallel shard of SURVEY 8e'}
 		if coll is not None:
 			out['collective'] = coll
-		if not args.headline_only:
+		if extras:
 			rf = dominant_roofline(run.dev, fp16=args.fp16)
 			full['roofline'] = dict(rf)
 			if not args.fp16:
@@ -1247,7 +1255,7 @@ def main():
 				out['cpu_baseline'] = dict(cb, sample=short(cb['sample'], 200))
 				out['x_cpu_baseline'] = out['value'] / cb['value']
 	del su
-	if run.world == 1 and not args.headline_only and not args.no_records:
+	if run.world == 1 and extras and not args.no_records:
 		recs = {}
 
 		def add(name, rec):
@@ -1282,15 +1290,13 @@ def main():
 		if 'error' in recs:
 			out['records_error'] = recs['error']
 	if run.rank == 0:
-		if full and not args.headline_only:
+		if extras:
 			full['line'] = out
-			for path in (RECORDS_FILE, os.path.join(ROOT, 'gpurun_out', 'bench_records.json')):
-				try:
-					if os.path.isdir(os.path.dirname(path)):
-						with open(path, 'w') as f:
-							json.dump(full, f, indent=1)
-				except OSError as e:
-					note(f'could not write {path}: {e}')
+			try:
+				with open(RECORDS_FILE, 'w') as f:
+					json.dump(full, f, indent=1)
+			except OSError as e:
+				note(f'could not write {RECORDS_FILE}: {e}')
 			out['records_file'] = os.path.basename(RECORDS_FILE)
 		text = json.dumps(out)
 		if len(text) >= LINE_LIMIT:   # never again a line the driver cannot parse: shed the optional keys, in this order

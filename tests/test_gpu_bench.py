@@ -1,5 +1,5 @@
-"""The driver's contract for bench.py: one JSON line on stdout with the metric of BASELINE.json, the timing fields, and the roofline /
-cpu_baseline objects of the hot-path tier.  (A short run: 3 timed steps, no extra records.)"""
+"""The driver's contract for bench.py: one JSON line on stdout with the metric of BASELINE.json and the timing fields; a plain run
+stops there, `--full` adds the roofline / cpu_baseline objects of the hot-path tier and the records of the other configurations."""
 import json
 import os
 import subprocess
@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_prints_one_json_line_with_the_contract_fields():
-	r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--no-records'],
+	r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--full', '--no-records'],
 					   capture_output=True, text=True, timeout=900, cwd=ROOT)
 	assert r.returncode == 0, r.stderr[-2000:]
 	lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -41,13 +41,37 @@ def test_bench_prints_one_json_line_with_the_contract_fields():
 	assert cb['value'] > 0 and cb['unit'] == d['unit'] and cb['cores'] >= 1 and cb['kind'] in ('reference', 'port') and isinstance(cb['sample'], str)
 
 
+def test_a_plain_run_measures_the_headline_alone():
+	"""Without --full the run sets up, primes, warms up, times the steps and prints the line: no roofline loop, CPU leg or records, no
+	bench_records.json, and at most 30 s of the whole process's wall time outside its W + K steps."""
+	import time
+	rec = os.path.join(ROOT, 'bench_records.json')
+	before = os.stat(rec).st_mtime_ns if os.path.exists(rec) else None
+	steps, warmup = 20, 5
+	t0 = time.perf_counter()
+	r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', str(steps), '--warmup', str(warmup)],
+					   capture_output=True, text=True, timeout=600, cwd=ROOT)
+	wall = time.perf_counter() - t0
+	assert r.returncode == 0, r.stderr[-2000:]
+	lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+	assert len(lines) == 1, r.stdout[-2000:]
+	d = json.loads(lines[0])
+	assert d['n_gpus'] == 1 and d['steps'] == steps and d['warmup'] == warmup and d['dtype'] == 'f32' and d['higher_is_better'] is True
+	assert d['unit'] == 'vertices*views/s' and abs(d['value'] - 16 * 6890 / (d['ms_per_step'] * 1e-3)) < 1e-6 * d['value']
+	assert not {'roofline', 'cpu_baseline', 'x_cpu_baseline', 'records', 'records_error', 'records_file', 'collective'} & set(d), sorted(d)
+	assert not any(ln.startswith('{"record"') for ln in r.stderr.splitlines())
+	assert (os.stat(rec).st_mtime_ns if os.path.exists(rec) else None) == before
+	outside = wall - (steps + warmup) * d['ms_per_step'] * 1e-3
+	assert outside <= 30.0, f'{outside:.1f} s outside the steps'
+
+
 @pytest.mark.timeout(1200)
 def test_the_drivers_exact_command_gives_one_short_parsable_line():
-	"""round 4's line was 20.5 kB (15 nested records) and the driver could not parse it.  This runs the command the driver
-	runs -- records on -- and holds the line to what a parser with a small buffer can take: stdout is ONE line under 4 kB that carries the
+	"""round 4's line was 20.5 kB (15 nested records) and the driver could not parse it.  This runs the driver's command
+	with --full -- records on, the longest line -- and holds it to what a parser with a small buffer can take: stdout is ONE line under 4 kB that carries the
 	contract fields, the records travel as name -> [ms_per_step, steps] on the line, in full in bench_records.json and as one short JSON
 	line each on stderr."""
-	r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '20', '--warmup', '5'],
+	r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '20', '--warmup', '5', '--full'],
 					   capture_output=True, text=True, timeout=1100, cwd=ROOT)
 	assert r.returncode == 0, r.stderr[-2000:]
 	lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -82,7 +106,7 @@ def test_two_rank_bench_path_runs_end_to_end_on_one_gpu():
 	env = dict(os.environ, FIND_BENCH_SHARE_GPU='1')
 	for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_PORT'):
 		env.pop(k, None)
-	r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--no-records'],
+	r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--full', '--no-records'],
 					   capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
 	assert r.returncode == 0, r.stderr[-3000:]
 	lines = [ln for ln in r.stdout.splitlines() if ln.strip().startswith('{')]
@@ -115,7 +139,7 @@ def test_four_rank_bench_path_runs_end_to_end_on_one_gpu():
 	env = dict(os.environ, FIND_BENCH_SHARE_GPU='1')
 	for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_PORT'):
 		env.pop(k, None)
-	r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', str(n), '--steps', '2', '--warmup', '1', '--no-records', '--no-prime'],
+	r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', str(n), '--steps', '2', '--warmup', '1', '--full', '--no-records', '--no-prime'],
 					   capture_output=True, text=True, timeout=1500, cwd=ROOT, env=env)
 	assert r.returncode == 0, r.stderr[-3000:]
 	lines = [ln for ln in r.stdout.splitlines() if ln.strip().startswith('{')]

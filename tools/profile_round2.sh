@@ -1,6 +1,6 @@
 #!/bin/bash
 # Round 2 evidence -> gpurun_out/r02/ (copy what is to be judged into profiles/):
-#   1. python bench.py (the driver's command) -> bench_line.json
+#   1. python bench.py --full (the driver's command, everything on) -> bench_line.json
 #   2. rocprofv3 --kernel-trace --stats of the headline loop alone (bench.py --headline-only) -> kernel stats of that command, and the
 #      steady-state statistics (warm-up launches dropped, tools/steady_stats.py)
 #   2b. the same for the batch-1 records (bench.py --train3d-b1): per-step statistics cut at the optimiser kernel (tools/step_stats.py)
@@ -11,10 +11,10 @@
 set -eu
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}; O=$R/gpurun_out/r02; mkdir -p $O
 cd $R
-timeout 900 python3 bench.py > $O/bench_line.json 2> $O/bench.err
+timeout 900 python3 bench.py --full > $O/bench_line.json 2> $O/bench.err
 cd /tmp; export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/headline -- python3 $R/bench.py --headline-only --steps 30 --warmup 10 > $O/headline_line.json 2> $O/headline.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/roofline -- python3 $R/bench.py --no-records --no-cpu-baseline > $O/roofline_line.json 2> $O/roofline.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/roofline -- python3 $R/bench.py --full --no-records --no-cpu-baseline > $O/roofline_line.json 2> $O/roofline.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/b1 -- python3 $R/bench.py --train3d-b1 --no-graph --no-cpu-baseline > $O/b1_line.json 2> $O/b1.err
 i=0
 for set in "SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_BUSY_CU_CYCLES" "FETCH_SIZE" "WRITE_SIZE"; do

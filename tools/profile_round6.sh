@@ -18,7 +18,7 @@ for w in $what; do
     cp "$O"/headline/*/*kernel_stats.csv "$O/headline_kernel_stats.csv"
     head -16 "$O/headline_steady_kernel_stats.csv" | cut -c1-150; tail -1 "$O/headline_step_stats.csv" ;;
   roofline)
-    rocprofv3 --kernel-trace --stats --output-format csv -d "$O/roofline" -- python3 "$R/bench.py" --no-records --no-cpu-baseline > "$O/roofline_line.json" 2> "$O/roofline.err"
+    rocprofv3 --kernel-trace --stats --output-format csv -d "$O/roofline" -- python3 "$R/bench.py" --full --no-records --no-cpu-baseline > "$O/roofline_line.json" 2> "$O/roofline.err"
     python3 "$R/tools/roofline_loop_stats.py" "$O"/roofline/*/*kernel_trace.csv "gemm7_kernel<1, 0, false, false>" > "$O/roofline_loop_kernel_stats.txt"; cat "$O/roofline_loop_kernel_stats.txt" ;;
   dw6)
     export FIND_TUNING=mlp_f16=2
