@@ -93,16 +93,23 @@ __global__ void sample_bwd_kernel(const int32_t* __restrict__ faces, int64_t fac
 // launches and a 13 776-element scan per mesh.  Here: face_areas_kernel (the vertex gathers spread over the whole chip), one block per
 // mesh turns the areas into their running sum in place (rounds of 16 384 faces, sixteen consecutive ones per thread, block scan of the
 // 1024 per-thread totals), then one thread per sample searches it with its own uniform draw r in [0,1): the first face whose running
-// sum exceeds r * total.  Faces of zero area (the -1 padding of ragged batches included) can never be that first face.
+// sum exceeds r * total.
+// The float32 partial sums of that order do not chain exactly: the value a thread starts from, base + (inc - a[15]), rounds differently
+// from the value the thread before it ended on.  So the stored sum is the running MAXIMUM of those partial sums, taken over the faces of
+// positive area only (a max scan in the same fixed order, exact): c[f] = c[f-1] for a face of zero area, max(partial sum, c[f-1])
+// otherwise, and the total c[n_faces-1] is the value at the last face of positive area.  The stored sum never decreases, is exactly flat
+// across every face of zero area, and so such a face (the -1 padding of ragged batches included) can never be the first face above a draw.
 // (Measured and dropped: areas computed inside the scan block -- one launch less, but a mesh's 13 776 x 12 scattered loads then go
 // through ONE CU's L1: 44 - 67 us against 5 + 12.)
 constexpr int CDF_PER = 16;
 __global__ __launch_bounds__(1024) void area_scan_kernel(int n_faces, float* __restrict__ cdf /* in: areas, out: their running sum */) {
 	__shared__ float wsum[16];
+	__shared__ float wmax[16];
 	float* out = cdf + (int64_t)blockIdx.x * n_faces;
 	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 	const bool vec = (n_faces & 3) == 0;   // rows of the (n_meshes, n_faces) buffer stay 16-byte aligned
 	float carry = 0.f;   // running sum of the faces before this round (the same value in every thread)
+	float carry_max = 0.f;   // the stored running sum at the last face before this round (every sum is >= 0: 0 is the identity of the max)
 	// a fixed order -- consecutive faces inside a thread, shuffles inside the wave, LDS across the 16 waves --, so the result is deterministic
 	for (int f0 = 0; f0 < n_faces; f0 += 1024 * CDF_PER) {
 		const int f = f0 + CDF_PER * (int)threadIdx.x;
@@ -117,6 +124,9 @@ __global__ __launch_bounds__(1024) void area_scan_kernel(int n_faces, float* __r
 #pragma unroll
 			for (int k = 0; k < CDF_PER; ++k) a[k] = f + k < n_faces ? out[f + k] : 0.f;
 		}
+		unsigned pos = 0;   // bit k: face f + k has positive area
+#pragma unroll
+		for (int k = 0; k < CDF_PER; ++k) pos |= (a[k] > 0.f ? 1u : 0u) << k;
 #pragma unroll
 		for (int k = 1; k < CDF_PER; ++k) a[k] += a[k - 1];
 		float inc = a[CDF_PER - 1];
@@ -134,16 +144,39 @@ __global__ __launch_bounds__(1024) void area_scan_kernel(int n_faces, float* __r
 			total += wsum[w];
 		}
 		const float off = base + (inc - a[CDF_PER - 1]);
+		// running max of the partial sums of positive-area faces: in the thread, then across the wave, the waves and the rounds
+		float mx = 0.f;
+#pragma unroll
+		for (int k = 0; k < CDF_PER; ++k) {
+			mx = fmaxf(mx, (pos >> k) & 1u ? off + a[k] : 0.f);
+			a[k] = mx;
+		}
+		float imx = mx;
+#pragma unroll
+		for (int o = 1; o < 64; o <<= 1) {
+			const float t = __shfl_up(imx, o, 64);
+			if (lane >= o) imx = fmaxf(imx, t);
+		}
+		const float left = __shfl_up(imx, 1, 64);   // the lanes before this one
+		if (lane == 63) wmax[wave] = imx;   // (the previous round's wmax reads are behind this round's first barrier)
+		__syncthreads();
+		float prev = lane > 0 ? fmaxf(carry_max, left) : carry_max, round_max = carry_max;
+		for (int w = 0; w < 16; ++w) {
+			if (w < wave) prev = fmaxf(prev, wmax[w]);
+			round_max = fmaxf(round_max, wmax[w]);
+		}
 		if (vec && f + CDF_PER <= n_faces) {
 #pragma unroll
 			for (int k = 0; k < CDF_PER; k += 4)
-				*reinterpret_cast<float4*>(out + f + k) = make_float4(off + a[k], off + a[k + 1], off + a[k + 2], off + a[k + 3]);
+				*reinterpret_cast<float4*>(out + f + k) =
+					make_float4(fmaxf(prev, a[k]), fmaxf(prev, a[k + 1]), fmaxf(prev, a[k + 2]), fmaxf(prev, a[k + 3]));
 		} else {
 #pragma unroll
 			for (int k = 0; k < CDF_PER; ++k)
-				if (f + k < n_faces) out[f + k] = off + a[k];
+				if (f + k < n_faces) out[f + k] = fmaxf(prev, a[k]);
 		}
 		carry = total;
+		carry_max = round_max;
 	}
 }
 
@@ -597,6 +630,10 @@ __global__ void nn_bwd_kernel(const float* __restrict__ x, const int32_t* __rest
 // cot = [(B2+C2-A2), (A2+C2-B2), (A2+B2-C2)] / area / 4;  L[v1,v2]+=cot_a, L[v2,v0]+=cot_b, L[v0,v1]+=cot_c, symmetrised.
 __global__ void cot_weights_kernel(const float* __restrict__ verts, const int32_t* __restrict__ faces, int n_verts, int n_faces,
 								   float* __restrict__ fw) {
+	// No fp contraction: the reference forms B2 + C2 - A2 from separately rounded squares, so a face with a zero-length edge (B == C)
+	// gives exactly 0, and a vertex in no other face gets a row sum of exactly 0 (the norm_w = rowsum branch).  Fused, C * C - B2 is the
+	// rounding error of B2, the row sum is +-1e-9 x the face's weights, and that vertex's |lap| jumps by |V| (tests/test_gpu_smooth_f64.py).
+#pragma clang fp contract(off)
 	const int m = blockIdx.y;
 	const int f = blockIdx.x * blockDim.x + threadIdx.x;
 	if (f >= n_faces) return;

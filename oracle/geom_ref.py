@@ -143,3 +143,68 @@ def mesh_smoothness(verts, faces, edges=None):
 	if edges is None:
 		edges = unique_edges(faces)
 	return 0.1 * mesh_laplacian_smoothing_cot(verts, faces) + 10 * mesh_edge_loss(verts, edges)
+
+
+# --------------------------------------------------------------------------------------------- smoothness, sparse (a14)
+def heron_product(verts1, faces):
+	"""s (s-A) (s-B) (s-C) per face of one mesh (the quantity ops/laplacian_matrices.py clamps at 1e-12 before its square root), and
+	the semi-perimeter s.  In the dtype of verts1."""
+	f = faces.long()
+	v0, v1, v2 = verts1[f[:, 0]], verts1[f[:, 1]], verts1[f[:, 2]]
+	A = (v1 - v2).norm(dim=1)
+	B = (v0 - v2).norm(dim=1)
+	C = (v0 - v1).norm(dim=1)
+	s = 0.5 * (A + B + C)
+	return s * (s - A) * (s - B) * (s - C), s
+
+
+def cot_entries(verts1, faces, eps=1e-12):
+	"""The 6F directed entries (row, col, weight) of the symmetric cotangent matrix of ops/laplacian_matrices.py for one mesh: face
+	(f0, f1, f2) adds cot_a/4 at (f1, f2), cot_b/4 at (f2, f0), cot_c/4 at (f0, f1), and L + L^T adds each again transposed.  Built
+	WITHOUT gradient, like the reference.  The same matrix as cot_laplacian_apply, never formed densely."""
+	with torch.no_grad():
+		f = faces.long()
+		v0, v1, v2 = verts1[f[:, 0]], verts1[f[:, 1]], verts1[f[:, 2]]
+		A = (v1 - v2).norm(dim=1)
+		B = (v0 - v2).norm(dim=1)
+		C = (v0 - v1).norm(dim=1)
+		s = 0.5 * (A + B + C)
+		area = (s * (s - A) * (s - B) * (s - C)).clamp(min=eps).sqrt()
+		A2, B2, C2 = A * A, B * B, C * C
+		cot = torch.stack([(B2 + C2 - A2) / area, (A2 + C2 - B2) / area, (A2 + B2 - C2) / area], dim=1) / 4.0
+		ii = f[:, [1, 2, 0]].reshape(-1)
+		jj = f[:, [2, 0, 1]].reshape(-1)
+		w = cot.reshape(-1)
+	return torch.cat([ii, jj]), torch.cat([jj, ii]), torch.cat([w, w])
+
+
+def cot_laplacian_apply_sparse(verts1, rows, cols, w):
+	"""(L @ V (V,3), rowsum (V,1)) from directed entries (cot_entries), by index_add; differentiable in verts1 through L @ V only."""
+	V = verts1.shape[0]
+	lv = torch.zeros(V, 3, dtype=verts1.dtype).index_add(0, rows, w[:, None] * verts1[cols])
+	with torch.no_grad():
+		rowsum = torch.zeros(V, dtype=verts1.dtype).index_add(0, rows, w)[:, None]
+	return lv, rowsum
+
+
+def laplacian_terms_sparse(verts1, faces, entries=None):
+	"""Per-vertex pieces of mesh_laplacian_smoothing(method='cot') for one mesh: lap = (L V) * norm_w - V (V,3) and (L V) * norm_w,
+	norm_w = 1/rowsum where rowsum > 0 (other values left as they are).  entries: directed (rows, cols, w), default cot_entries."""
+	rows, cols, w = cot_entries(verts1, faces) if entries is None else entries
+	lv, rowsum = cot_laplacian_apply_sparse(verts1, rows, cols, w)
+	with torch.no_grad():
+		norm_w = rowsum.clone()
+		pos = norm_w > 0
+		norm_w[pos] = 1.0 / norm_w[pos]
+	lvn = lv * norm_w
+	return lvn - verts1, lvn
+
+
+def mesh_laplacian_smoothing_cot_sparse(verts, faces):
+	"""mesh_laplacian_smoothing_cot without the V x V matrix: float64 or float32, any V."""
+	N, V, _ = verts.shape
+	total = 0
+	for n in range(N):
+		lap, _ = laplacian_terms_sparse(verts[n], faces)
+		total = total + lap.norm(dim=1).sum() / V
+	return total / N
