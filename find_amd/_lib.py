@@ -118,6 +118,9 @@ PROTOTYPES = {
 	'find_render_fwd': (c_int, [POINTER(RenderParams), _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P]),
 	'find_render_bwd': (c_int, [POINTER(RenderParams), _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P]),
 	'find_render_flags': (c_int, [_P, _P, _P]),
+	'find_render_features_ws_bytes': (c_int64, [POINTER(RenderParams), _I, _I, _I]),
+	'find_render_features_fwd': (c_int, [POINTER(RenderParams), _P, _P, _I, _P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _I, _P, _I, _P]),
+	'find_render_features_bwd': (c_int, [POINTER(RenderParams), _P, _P, _I, _P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _I, _P, _I, _P]),
 	'find_points_render': (c_int, [POINTER(PointsParams), _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
 }
 # include/find_hip_diag.h: what libfind_hip_diag.so exports on top

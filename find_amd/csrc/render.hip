@@ -30,7 +30,9 @@
 // triangles by face_setup_kernel<true>; every per-face array then holds 2 F SLOTS per image, steps 3-5 run over slots unchanged,
 // clip_frag_kernel converts the nearest fragment back to the original face, clip_chain_kernel takes the clipped slots' gradients back.
 // Conventions: SURVEY.md Appendix A.2-A.4 (row-vector transforms, NDC +x left / +y up, image = mesh*n_views + view).
+#include <mutex>
 #include <type_traits>
+#include <unordered_map>
 
 #include "common.h"
 
@@ -1953,8 +1955,23 @@ __global__ void cam_center_kernel(const float* __restrict__ R, const float* __re
 }  // namespace render
 }  // namespace find
 
+#include "render_features.h"
+
 using namespace find;
 using namespace find::render;
+
+// What the last find_render_fwd into a workspace rendered: the feature render reads that forward's K-set and tile lists, which exist
+// only where it formed the mask (the RGB-only pass bins with blur 0 and leaves zthr unwritten).  Host-side, keyed by the workspace
+// address, so that the check costs no synchronisation.
+namespace {
+struct WsStamp {
+	int64_t n_meshes, n_views, n_verts, n_faces;
+	int32_t image_h, image_w;
+	bool mask;
+};
+std::mutex g_stamp_mu;
+std::unordered_map<const void*, WsStamp> g_stamps;
+}  // namespace
 
 static int check_params(const find_render_params* rp, int64_t n_meshes, int64_t n_views, int64_t V, int64_t F) {
 	FIND_REQUIRE(rp != nullptr, "find_render: params is NULL");
@@ -1987,6 +2004,10 @@ extern "C" int find_render_fwd(const find_render_params* rp, const float* verts,
 	Ws w;
 	carve(rp, n_meshes, n_views, n_verts, n_faces, ws, &w);
 	if (ws_bytes < find_render_ws_bytes(rp, n_meshes, n_views, n_verts, n_faces)) { set_error("find_render_fwd: workspace too small"); return FIND_EWORKSPACE; }
+	{
+		std::lock_guard<std::mutex> lk(g_stamp_mu);
+		g_stamps[ws] = WsStamp{n_meshes, n_views, n_verts, n_faces, rp->image_h, rp->image_w, mask != nullptr};
+	}
 	float* cam = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + w.bytes);
 	hipStream_t s = (hipStream_t)stream;
 	const int64_t n_img = n_meshes * n_views;
@@ -2235,5 +2256,111 @@ extern "C" int find_render_frags(const find_render_params* rp, int64_t n_meshes,
 		set_error("find_render_frags: copy failed");
 		return FIND_ELAUNCH;
 	}
+	return FIND_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ per-vertex feature render
+// render_features.h: FeatureShader + softmax_blend on the silhouette fragments of the find_render_fwd that used `ws`.
+static int check_features(const char* who, const find_render_params* rp, const void* ws, int64_t ws_bytes, int64_t n_meshes, int64_t n_views,
+						  int64_t n_verts, int64_t n_faces, int64_t n_channels, const void* fws, int64_t fws_bytes) {
+	int rc = check_params(rp, n_meshes, n_views, n_verts, n_faces);
+	if (rc != FIND_OK) return rc;
+	FIND_REQUIRE(rp->clip_faces == 0, "%s: clip_faces = 1 (split mode) is not supported by the feature render", who);
+	FIND_REQUIRE(n_channels >= 1 && n_channels <= 65536, "%s: n_channels %lld outside 1 .. 65536", who, (long long)n_channels);
+	FIND_REQUIRE(ws && fws, "%s: NULL workspace", who);
+	{
+		std::lock_guard<std::mutex> lk(g_stamp_mu);
+		const auto it = g_stamps.find(ws);
+		FIND_REQUIRE(it != g_stamps.end() && it->second.mask, "%s: the workspace does not hold a find_render_fwd with a mask (the feature render reads its K nearest silhouette candidates)", who);
+		const WsStamp& st = it->second;
+		FIND_REQUIRE(st.n_meshes == n_meshes && st.n_views == n_views && st.n_verts == n_verts && st.n_faces == n_faces && st.image_h == rp->image_h &&
+					 st.image_w == rp->image_w, "%s: the workspace's forward rendered another geometry", who);
+	}
+	if (ws_bytes < find_render_ws_bytes(rp, n_meshes, n_views, n_verts, n_faces) || fws_bytes < find_render_features_ws_bytes(rp, n_meshes, n_views, n_channels)) {
+		set_error("%s: workspace too small", who);
+		return FIND_EWORKSPACE;
+	}
+	return FIND_OK;
+}
+
+static FeatArgs feat_args(const find_render_params* rp, const Ws& w, const int32_t* faces, int64_t faces_batch, int64_t n_meshes, int64_t n_views,
+						  int64_t n_verts, int64_t n_faces, const float* features, int64_t n_channels, float* out, void* fws) {
+	FeatArgs a;
+	memset(&a, 0, sizeof(a));
+	a.recs = w.recs; a.frec = w.frec; a.tb = w.tb; a.zinfo = w.zinfo; a.tinfo = w.tinfo; a.pool = w.pool; a.pool_cap = w.pool_cap;
+	a.zthr = w.zthr; a.tie_face = w.tie_face;
+	a.faces = faces; a.faces_mesh_stride = faces_batch == 1 ? 0 : n_faces * 3;
+	a.feat = features; a.out = out; a.fpix = reinterpret_cast<float4*>(fws);
+	a.C = (int)n_channels; a.V = (int)n_verts; a.F = (int)n_faces; a.n_views = (int)n_views; a.H = rp->image_h; a.W = rp->image_w;
+	a.tiles_x = (int)cdiv(a.W, T8); a.tiles_per_img = a.tiles_x * (int)cdiv(a.H, T8); a.total_tiles = (int)(a.tiles_per_img * n_meshes * n_views);
+	a.blur = rp->sil_blur_radius; a.inv_sigma = 1.0f / rp->rgb_sigma; a.gamma = rp->rgb_gamma;
+	a.ablate = find::g_raster_ablate;
+	return a;
+}
+
+extern "C" int64_t find_render_features_ws_bytes(const find_render_params* rp, int64_t n_meshes, int64_t n_views, int64_t n_channels) {
+	if (!rp || rp->image_h < 1 || rp->image_w < 1 || n_meshes < 1 || n_views < 1 || n_channels < 1) return -1;
+	return n_meshes * n_views * rp->image_h * rp->image_w * (int64_t)sizeof(float4);
+}
+
+extern "C" int find_render_features_fwd(const find_render_params* rp, const float* verts, const int32_t* faces, int64_t faces_batch, const float* R,
+										const float* T, int64_t n_meshes, int64_t n_views, int64_t n_verts, int64_t n_faces, const float* features,
+										int64_t n_channels, float* out, const void* ws, int64_t ws_bytes, void* fws, int64_t fws_bytes, void* stream) {
+	int rc = check_features("find_render_features_fwd", rp, ws, ws_bytes, n_meshes, n_views, n_verts, n_faces, n_channels, fws, fws_bytes);
+	if (rc != FIND_OK) return rc;
+	FIND_REQUIRE(verts && faces && R && T && features && out, "find_render_features_fwd: NULL argument");
+	FIND_REQUIRE(faces_batch == 1 || faces_batch == n_meshes, "find_render_features_fwd: faces_batch must be 1 or n_meshes");
+	Ws w;
+	carve(rp, n_meshes, n_views, n_verts, n_faces, const_cast<void*>(ws), &w);
+	const FeatArgs a = feat_args(rp, w, faces, faces_batch, n_meshes, n_views, n_verts, n_faces, features, n_channels, out, fws);
+	for (int c0 = 0; c0 < a.C; c0 += FEAT_CC)   // (the first launch settles the nearest depth and the denominator the others read)
+		hipLaunchKernelGGL(feat_fwd_kernel, dim3((unsigned)a.total_tiles), dim3(64), 0, (hipStream_t)stream, a, c0);
+	FIND_LAUNCH_CHECK("find_render_features_fwd");
+	return FIND_OK;
+}
+
+template <int LPF>
+static void feat_bwd_launch(const FeatArgs& a, int64_t n_img, const float* d_out, float* d_vproj, float* d_feat, hipStream_t s) {
+	const dim3 grid((unsigned)cdiv(a.F, 256 / LPF), (unsigned)n_img);
+	for (int c0 = 0; c0 < a.C; c0 += FEAT_CC) {
+		const bool geom = d_vproj && c0 == 0;
+		if (geom && d_feat) hipLaunchKernelGGL((feat_bwd_kernel<LPF, true, true>), grid, dim3(256), 0, s, a, d_out, c0, d_vproj, d_feat);
+		else if (geom) hipLaunchKernelGGL((feat_bwd_kernel<LPF, true, false>), grid, dim3(256), 0, s, a, d_out, c0, d_vproj, d_feat);
+		else if (d_feat) hipLaunchKernelGGL((feat_bwd_kernel<LPF, false, true>), grid, dim3(256), 0, s, a, d_out, c0, d_vproj, d_feat);
+		if (!d_feat) break;
+	}
+}
+
+extern "C" int find_render_features_bwd(const find_render_params* rp, const float* verts, const int32_t* faces, int64_t faces_batch, const float* R,
+										const float* T, int64_t n_meshes, int64_t n_views, int64_t n_verts, int64_t n_faces, const float* features,
+										int64_t n_channels, const float* out, const float* d_out, float* d_verts, float* d_features, void* ws,
+										int64_t ws_bytes, void* fws, int64_t fws_bytes, void* stream) {
+	int rc = check_features("find_render_features_bwd", rp, ws, ws_bytes, n_meshes, n_views, n_verts, n_faces, n_channels, fws, fws_bytes);
+	if (rc != FIND_OK) return rc;
+	FIND_REQUIRE(verts && faces && R && T && features && out && d_out, "find_render_features_bwd: NULL argument");
+	FIND_REQUIRE(d_verts || d_features, "find_render_features_bwd: no gradient requested");
+	FIND_REQUIRE(faces_batch == 1 || faces_batch == n_meshes, "find_render_features_bwd: faces_batch must be 1 or n_meshes");
+	Ws w;
+	carve(rp, n_meshes, n_views, n_verts, n_faces, ws, &w);
+	hipStream_t s = (hipStream_t)stream;
+	const int64_t n_img = n_meshes * n_views, n_px = n_img * rp->image_h * rp->image_w;
+	const FeatArgs a = feat_args(rp, w, faces, faces_batch, n_meshes, n_views, n_verts, n_faces, features, n_channels, nullptr, fws);
+	if (d_features) (void)hipMemsetAsync(d_features, 0, n_meshes * n_verts * n_channels * sizeof(float), s);
+	if (d_verts) {
+		(void)hipMemsetAsync(w.d_vproj, 0, n_img * n_verts * 3 * sizeof(float), s);
+		hipLaunchKernelGGL(feat_gdot_kernel, dim3((unsigned)cdiv(n_px, 256)), dim3(256), 0, s, out, d_out, n_px, (int)n_channels, a.fpix);
+	}
+	float* dvp = d_verts ? w.d_vproj : nullptr;
+	// lanes per face by the size of a typical blurred bbox, as find_render_bwd's silhouette part
+	const float side = 2.0f * sqrtf(rp->sil_blur_radius) * 0.5f * (float)std::max(rp->image_h, rp->image_w) + 2.0f;
+	if (side * side > 640.0f) feat_bwd_launch<32>(a, n_img, d_out, dvp, d_features, s);
+	else if (side * side > 160.0f) feat_bwd_launch<16>(a, n_img, d_out, dvp, d_features, s);
+	else feat_bwd_launch<8>(a, n_img, d_out, dvp, d_features, s);
+	if (d_verts) {
+		const float sc = 1.0f / tanf(rp->fov_deg * 3.14159265358979323846f / 180.0f * 0.5f);
+		hipLaunchKernelGGL(project_bwd_kernel, dim3((unsigned)cdiv(n_verts, 256), (unsigned)n_meshes), dim3(256), 0, s, verts, R, T, sc, (int)n_views,
+						   (int)n_verts, w.d_vproj, d_verts, 1);
+	}
+	FIND_LAUNCH_CHECK("find_render_features_bwd");
 	return FIND_OK;
 }

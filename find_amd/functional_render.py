@@ -1,5 +1,5 @@
-"""torch.autograd binding of the HIP renderer (find_render_fwd / find_render_bwd) and the keypoint splat render (find_points_render,
-forward only).  GPU only, no fallback."""
+"""torch.autograd binding of the HIP renderer (find_render_fwd / find_render_bwd), of the per-vertex feature render on its raster pass
+(find_render_features_fwd / _bwd) and of the keypoint splat render (find_points_render, forward only).  GPU only, no fallback."""
 import atexit
 import contextlib
 import ctypes
@@ -220,11 +220,91 @@ class _Render(torch.autograd.Function):
 		return d_verts, d_colors, None, None, None, None, None, None, None
 
 
-def render(verts, colors, faces, R, T, params, want_mask=True, want_image=True, want_frags=False):
+class _RenderFeatures(torch.autograd.Function):
+	"""_Render plus the per-vertex feature render (find_render_features_fwd / _bwd) on the same raster pass: the forward always forms the
+	mask (the feature render reads its K nearest silhouette candidates) and returns it only when asked for."""
+	@staticmethod
+	def forward(ctx, verts, colors, features, faces, R, T, params, want_mask, want_image, want_frags):
+		_require_gpu(verts, colors, features, R, T)
+		if params.clip_faces:
+			raise NotImplementedError('find_amd.render: per-vertex features are not rendered in split mode (clip_faces=True): the feature '
+									  'shader reads the K nearest silhouette candidates of unclipped faces')
+		L = _lib.lib()
+		verts, colors, features, R, T = _c(verts), _c(colors), _c(features), _c(R), _c(T)
+		faces = _faces_i32(faces)
+		N, V, _ = verts.shape
+		M = R.shape[0]
+		C = features.shape[-1]
+		fb = 1 if faces.dim() == 2 else faces.shape[0]
+		F = faces.shape[-2]
+		H, W = params.image_h, params.image_w
+		dev = verts.device
+		nbytes = L.find_render_ws_bytes(ctypes.byref(params), N, M, V, F)
+		fbytes = L.find_render_features_ws_bytes(ctypes.byref(params), N, M, C)
+		if nbytes < 0 or fbytes < 0:
+			check(-1, 'find_render_ws_bytes')
+		ws, fws = _ws(nbytes, dev), _ws(fbytes, dev)
+		mask = torch.empty(N, M, H, W, device=dev)
+		image = torch.empty(N, M, H, W, 3, device=dev) if want_image else None
+		p2f = torch.empty(N, M, H, W, device=dev, dtype=torch.int32) if want_frags else None
+		zbuf = torch.empty(N, M, H, W, device=dev) if want_frags else None
+		feat = torch.empty(N, M, H, W, C, device=dev)
+		stream = current_stream(dev)
+		check(L.find_render_fwd(ctypes.byref(params), ptr(verts), ptr(faces), fb, ptr(colors), ptr(R), ptr(T), N, M, V, F, ptr(mask), ptr(image),
+								ptr(p2f), ptr(zbuf), ptr(ws), ws.numel(), stream), 'find_render_fwd')
+		check(L.find_render_features_fwd(ctypes.byref(params), ptr(verts), ptr(faces), fb, ptr(R), ptr(T), N, M, V, F, ptr(features), C, ptr(feat),
+										 ptr(ws), ws.numel(), ptr(fws), fws.numel(), stream), 'find_render_features_fwd')
+		_watch(ws, f'render of {N} meshes x {M} views @{H}x{W} with {C} feature channels')
+		ctx.params, ctx.ws, ctx.fws, ctx.dims = params, ws, fws, (N, M, V, F, fb, C)
+		ctx.save_for_backward(verts, colors, features, faces, R, T, mask, feat)
+		ctx.mark_non_differentiable(*[t for t in (p2f, zbuf) if t is not None])
+		ctx.set_materialize_grads(False)
+		return (mask if want_mask else None), image, p2f, zbuf, feat
+
+	@staticmethod
+	def backward(ctx, g_mask, g_image, _gp, _gz, g_feat):
+		L = _lib.lib()
+		verts, colors, features, faces, R, T, mask, feat = ctx.saved_tensors
+		N, M, V, F, fb, C = ctx.dims
+		stream = current_stream(verts.device)
+		d_verts = d_colors = d_features = None
+		if g_mask is not None or g_image is not None:
+			g_mask, g_image = _c(g_mask), _c(g_image)
+			d_verts = torch.empty_like(verts)
+			d_colors = torch.empty_like(colors) if (colors is not None and g_image is not None and ctx.needs_input_grad[1]) else None
+			check(L.find_render_bwd(ctypes.byref(ctx.params), ptr(verts), ptr(faces), fb, ptr(colors), ptr(R), ptr(T), N, M, V, F, ptr(mask),
+									ptr(g_mask), ptr(g_image), ptr(d_verts), ptr(d_colors), ptr(ctx.ws), ctx.ws.numel(), stream), 'find_render_bwd')
+		if g_feat is not None and (ctx.needs_input_grad[0] or ctx.needs_input_grad[2]):
+			g_feat = _c(g_feat)
+			if d_verts is None and ctx.needs_input_grad[0]:
+				d_verts = torch.zeros_like(verts)
+			d_features = torch.empty_like(features) if ctx.needs_input_grad[2] else None
+			check(L.find_render_features_bwd(ctypes.byref(ctx.params), ptr(verts), ptr(faces), fb, ptr(R), ptr(T), N, M, V, F, ptr(features), C,
+											 ptr(feat), ptr(g_feat), ptr(d_verts), ptr(d_features), ptr(ctx.ws), ctx.ws.numel(), ptr(ctx.fws),
+											 ctx.fws.numel(), stream), 'find_render_features_bwd')
+		return d_verts, d_colors, d_features, None, None, None, None, None, None, None
+
+
+def _check_features(features, verts):
+	if not isinstance(features, torch.Tensor) or not features.is_floating_point():
+		raise ValueError('find_amd.render: features must be a float tensor (N,V,C)')
+	if features.dim() != 3 or features.shape[0] != verts.shape[0] or features.shape[1] != verts.shape[1] or features.shape[2] < 1:
+		raise ValueError(f'find_amd.render: features must be (N,V,C) = ({verts.shape[0]},{verts.shape[1]},C >= 1), got {tuple(features.shape)}')
+	if features.device != verts.device or not features.is_cuda:
+		raise ValueError(f'find_amd.render: features must be on the mesh\'s ROCm device, got features on {features.device}, the mesh on {verts.device}')
+	return features.float()
+
+
+def render(verts, colors, faces, R, T, params, want_mask=True, want_image=True, want_frags=False, features=None):
 	"""verts (N,V,3), colors (N,V,3)|None, faces (F,3)|(N,F,3), R (M,3,3), T (M,3)  ->  mask (N,M,H,W), image (N,M,H,W,3),
-	pix_to_face (N,M,H,W) int32, zbuf (N,M,H,W)   (entries not requested are None)."""
+	pix_to_face (N,M,H,W) int32, zbuf (N,M,H,W)   (entries not requested are None).
+	features (N,V,C): also the feature maps (N,M,H,W,C) as a fifth entry -- FeatureShader + softmax_blend (znear 1, zfar 100, background 0)
+	on the K-nearest silhouette fragments, differentiable in the features and the vertices, from the same raster pass."""
 	if want_image and colors is None:
 		raise RuntimeError('find_amd.render: an RGB image needs per-vertex colours')
+	if features is not None:
+		features = _check_features(features, verts)
+		return _RenderFeatures.apply(verts, colors, features, faces, R, T, params, want_mask, want_image, want_frags)
 	return _Render.apply(verts, colors, faces, R, T, params, want_mask, want_image, want_frags)
 
 
@@ -265,17 +345,21 @@ def render_frags(ws, params, n_meshes, n_views, n_verts, n_faces):
 	return f, b
 
 
-def render_uv(verts, tex, faces, R, T, params, want_mask=True, want_frags=False):
+def render_uv(verts, tex, faces, R, T, params, want_mask=True, want_frags=False, features=None):
 	"""FootRenderer image of UV-textured meshes (GT scans; no gradient): the Phong + softmax blend is linear in the texture colour, so
 	image = o0 + (o1 - o0) * texel with o0 / o1 the renders with black / white vertex colours and texel the map read at every pixel's
-	nearest fragment.  Returns (mask, image, pix_to_face, zbuf)."""
+	nearest fragment.  Returns (mask, image, pix_to_face, zbuf), and with features (N,V,C) the feature maps (N,M,H,W,C) as a fifth entry."""
 	with torch.no_grad():
 		N, V, _ = verts.shape
 		M = R.shape[0]
 		Fn = faces.shape[-2]
 		ones = torch.ones(N, V, 3, device=verts.device)
 		L = _lib.lib()
-		mask, o1, p2f, zbuf = _Render.apply(verts, ones, faces, R, T, params, want_mask, True, True)
+		if features is not None:
+			features = _check_features(features, verts)
+			mask, o1, p2f, zbuf, feat = _RenderFeatures.apply(verts, ones, features, faces, R, T, params, want_mask, True, True)
+		else:
+			mask, o1, p2f, zbuf = _Render.apply(verts, ones, faces, R, T, params, want_mask, True, True)
 		# the fragments of that forward (its workspace is not exposed by autograd.Function: run the raster once more for the buffers)
 		vv, ff = _c(verts), _faces_i32(faces)
 		fb = 1 if ff.dim() == 2 else ff.shape[0]
@@ -288,7 +372,8 @@ def render_uv(verts, tex, faces, R, T, params, want_mask=True, want_frags=False)
 		H, W = params.image_h, params.image_w
 		texel = uv_sample(tex.maps_padded(), tex.verts_uvs_padded(), tex.faces_uvs_padded(), fl.reshape(N, M * H * W), bary.reshape(N, M * H * W, 3))
 		image = o0 + (o1 - o0) * texel.reshape(N, M, H, W, 3)
-	return mask, image, (p2f if want_frags else None), (zbuf if want_frags else None)
+	out = (mask, image, (p2f if want_frags else None), (zbuf if want_frags else None))
+	return out + (feat,) if features is not None else out
 
 
 def render_points(points, features, R, T, image_size, radius=0.03, points_per_pixel=10, fov_deg=60.0, return_fragments=False):

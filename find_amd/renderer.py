@@ -1,7 +1,8 @@
 """FootRenderer on the MI355X hot path: host-side mirror of reference src/model/renderer.py (same class name, constructor
 keywords, view helpers and forward() keywords / outputs); all rendering arithmetic runs in libfind_hip.so
 (find_amd.functional_render).  Keypoints are drawn as PyTorch3D's point renderer draws them (functional_render.render_points, one HIP
-kernel); the N-channel feature shader is out of scope."""
+kernel); per-vertex features (return_features=True, features=(N,V,C)) as FeatureShader draws them on the K-nearest silhouette fragments
+(find_render_features_fwd / _bwd, on the same raster pass as the mask and the image)."""
 from typing import Union
 
 import numpy as np
@@ -87,14 +88,30 @@ class FootRenderer(nn.Module):
 		no depth test against the mesh, no gradient) -- mesh n's keypoints in each of its M views, as renderer.py:367 meant (upstream's own
 		line discards that expansion and works for M = 1 only); with keypoints_blend also out['keypoints_blend'], the image with the
 		splats over it (~any(pcl > 0) * image + any(pcl > 0) * pcl), which needs return_images.  keypoints_blend without keypoints is
-		ignored, as upstream."""
+		ignored, as upstream.
+		return_features with features (N,V,C): out['features'] (N,M,H,W,C), the per-vertex features blended as FeatureShader does
+		(renderer.py:293-299: softmax_blend over the K = 100 silhouette fragments, znear 1, zfar 100, background 0), differentiable in the
+		features and the vertices; 0 where mask_out_faces hides a pixel.  Upstream needs return_mask=True as well (fragments['sil'] only
+		exists then); here the silhouette pass runs either way and out['mask'] is returned only when asked for.  Not in split mode
+		(clip_faces=True)."""
 		if keypoints is not None:
 			if keypoints_blend and not return_images:   # (a NameError upstream)
 				raise ValueError('FootRenderer: keypoints_blend draws the keypoints over the image: it needs return_images=True')
 			if keypoints.dim() != 3 or keypoints.shape[-1] != 3 or keypoints.shape[0] != len(input_meshes):
 				raise ValueError(f'FootRenderer: keypoints must be (N,P,3) with N = {len(input_meshes)} meshes, got {tuple(keypoints.shape)}')
-		if return_features or features is not None:
-			raise NotImplementedError('per-vertex feature rendering needs the restyle encoder and is out of scope')
+		if return_features:
+			if features is None:   # (an assert upstream)
+				raise ValueError('FootRenderer: return_features needs features (N,V,C)')
+			if self.params.clip_faces:
+				raise NotImplementedError('FootRenderer: per-vertex features are not rendered with clip_faces=True: the feature shader reads '
+										  'the K nearest silhouette candidates of unclipped faces (split mode is out of scope for it)')
+			nv = input_meshes.verts_padded().shape[:2]
+			if (not isinstance(features, torch.Tensor) or not features.is_floating_point() or features.dim() != 3
+					or tuple(features.shape[:2]) != tuple(nv) or features.shape[2] < 1):
+				raise ValueError(f'FootRenderer: features must be a float tensor (N,V,C) with N = {nv[0]} meshes and V = {nv[1]} vertices, got '
+								 + (f'{tuple(features.shape)} {features.dtype}' if isinstance(features, torch.Tensor) else type(features).__name__))
+			if features.device != input_meshes.device or not features.is_cuda:
+				raise ValueError(f'FootRenderer: features must be on the mesh\'s ROCm device ({input_meshes.device}), got {features.device}')
 		if lights is not None:
 			raise NotImplementedError('custom lights are not used on the FIND path; the renderer keeps PointLights((0,0,100))')
 		dev = input_meshes.device
@@ -115,16 +132,19 @@ class FootRenderer(nn.Module):
 		want_soft = return_mask and (mask_with_grad or not return_images)
 		# (pix_to_face is read below only to hide faces: when the caller names some, or for UV textures' (0,0)-UV convention)
 		want_frags = (mask_out_faces and (masked_faces is not None or uv_tex)) or return_depth
-		if not (return_images or want_soft or want_frags):
+		if not (return_images or want_soft or want_frags or return_features):
 			return self._keypoints(dict(), None, keypoints, keypoints_blend, R, T, dev)
 		if return_images and uv_tex:
 			# GT scans (dataset.py:263-271): no gradient flows to a UV-textured mesh anywhere in the reference
 			if verts.requires_grad:
 				raise NotImplementedError('UV-textured meshes are rendered without gradient (GT scans); use TexturesVertex for predicted meshes')
-			mask, renders, p2f, zbuf = FR.render_uv(verts, tex, faces, R, T, self.params, want_mask=want_soft, want_frags=want_frags)
+			res = FR.render_uv(verts, tex, faces, R, T, self.params, want_mask=want_soft, want_frags=want_frags,
+							   features=features if return_features else None)
 		else:
-			mask, renders, p2f, zbuf = FR.render(verts, colors, faces, R, T, self.params, want_mask=want_soft, want_image=return_images,
-												 want_frags=want_frags)
+			res = FR.render(verts, colors, faces, R, T, self.params, want_mask=want_soft, want_image=return_images, want_frags=want_frags,
+							features=features if return_features else None)
+		mask, renders, p2f, zbuf = res[:4]
+		feat = res[4] if return_features else None
 		out = dict()
 		if return_depth:
 			out['depth'] = zbuf
@@ -155,6 +175,8 @@ class FootRenderer(nn.Module):
 				renders = torch.where(mask_out.unsqueeze(-1), torch.ones_like(renders), renders)
 			if return_mask:
 				mask = torch.where(mask_out, torch.zeros_like(mask), mask)
+			if return_features:   # (renderer.py:361-363)
+				feat = torch.where(mask_out.unsqueeze(-1), torch.zeros_like(feat), feat)
 
 		self._keypoints(out, renders, keypoints, keypoints_blend, R, T, dev)
 		if return_images:
@@ -164,6 +186,8 @@ class FootRenderer(nn.Module):
 		if return_mask_out_masks:
 			out['mask_out_masks'] = mask_out
 			out['nothing_hidden'] = nothing_hidden
+		if return_features:
+			out['features'] = feat
 		return out
 
 	def _keypoints(self, out, renders, keypoints, keypoints_blend, R, T, dev):

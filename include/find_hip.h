@@ -518,6 +518,29 @@ int find_render_frags(const find_render_params* rp, int64_t n_meshes, int64_t n_
 					  int32_t* face_local, float* bary, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Per-vertex feature render (FootRenderer.forward(..., return_features=True, features=...), src/model/renderer.py:293-299).
+ * Replaces FeatureShader.forward (renderer.py:74-105) on fragments['sil']: [P3D-recall] TexturesVertex(features).sample_textures
+ * (interpolate_face_attributes with the clipped, perspective-correct barycentrics of the K = sil_faces_per_pixel, blurred pass) and
+ * softmax_blend (renderer.py:23-72) with its DEFAULT znear = 1, zfar = 100 -- not the camera's znear --, sigma = rgb_sigma, gamma =
+ * rgb_gamma and a background of C zeros.  features (n_meshes,n_verts,C) fp32; out (n_meshes,n_views,H,W,C), 0 where no fragment.
+ * `ws` must come from a find_render_fwd WITH a mask (its K nearest silhouette candidates per pixel and its tile lists are read) of the same
+ * geometry, untouched since; a workspace without one is refused (FIND_EINVAL), as are clip_faces = 1 and n_channels < 1.  `fws`
+ * (find_render_features_ws_bytes) carries per-pixel state from the forward to the backward.  No host synchronisation; the forward uses
+ * no atomics (repeated calls are bit-identical).
+ * find_render_features_bwd: d_out (like out) upstream gradient; `out` the forward's output.  d_verts (n_meshes,n_verts,3) is ADDED TO
+ * (find_render_bwd overwrites it: call that first when the mask or image has a gradient too), d_features (n_meshes,n_verts,C) is
+ * OVERWRITTEN, summed over the views; either may be NULL, not both.  It reuses the projection gradient buffer of `ws`.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t find_render_features_ws_bytes(const find_render_params* rp, int64_t n_meshes, int64_t n_views, int64_t n_channels);
+int find_render_features_fwd(const find_render_params* rp, const float* verts, const int32_t* faces, int64_t faces_batch, const float* R,
+							 const float* T, int64_t n_meshes, int64_t n_views, int64_t n_verts, int64_t n_faces, const float* features,
+							 int64_t n_channels, float* out, const void* ws, int64_t ws_bytes, void* fws, int64_t fws_bytes, void* stream);
+int find_render_features_bwd(const find_render_params* rp, const float* verts, const int32_t* faces, int64_t faces_batch, const float* R,
+							 const float* T, int64_t n_meshes, int64_t n_views, int64_t n_verts, int64_t n_faces, const float* features,
+							 int64_t n_channels, const float* out, const float* d_out, float* d_verts, float* d_features, void* ws,
+							 int64_t ws_bytes, void* fws, int64_t fws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Fused multi-tensor optimiser steps.  Replace torch.optim.Adam / torch.optim.SGD(momentum=0.9)
  * as constructed by the reference (src/train/train.py:161-168) and stepped once per batch
  * (src/train/trainer.py:121-123).  `param`, `grad`, moment arrays: HOST arrays of n_tensors DEVICE pointers (fp32,
