@@ -507,6 +507,48 @@ def weighted_terms(terms, weights):
 	return total, [scaled[i] for i in range(len(terms))]
 
 
+class _ContrastivePose(torch.autograd.Function):
+	"""sum_p [y d^2 + (1 - y) max(margin - d^2, 0)^2] / P over drawn pairs (ContrastiveLoss, reference losses.py:305-333): one launch each
+	way (find_contrastive_fwd / _bwd); the gradient goes to vecs only (codes are labels, pairs indices)."""
+
+	@staticmethod
+	def forward(ctx, vecs, codes, pairs, margin):
+		_require_gpu(vecs, codes, pairs)
+		L = _lib.lib()
+		if vecs.dim() != 2 or codes.dim() != 2 or codes.shape[0] != vecs.shape[0] or codes.dtype != torch.float32:
+			raise RuntimeError(f'find_amd.contrastive_pose: vecs (N, K) and fp32 codes (N, C) expected, got {tuple(vecs.shape)} / {tuple(codes.shape)} {codes.dtype}')
+		if pairs.dim() != 2 or pairs.shape[1] != 2 or pairs.dtype != torch.int32:
+			raise RuntimeError(f'find_amd.contrastive_pose: int32 pairs (P, 2) expected, got {tuple(pairs.shape)} {pairs.dtype}')
+		N, K = vecs.shape
+		P = pairs.shape[0]
+		if N < 2 or not 1 <= P <= N * (N - 1):
+			raise RuntimeError(f'find_amd.contrastive_pose: {P} pairs of {N} rows (N >= 2, 1 <= P <= N(N-1))')
+		vecs, codes, pairs = _c(vecs), _c(codes.detach()), _c(pairs)
+		loss = torch.empty((), device=vecs.device, dtype=torch.float32)
+		coef = torch.empty(P, device=vecs.device, dtype=torch.float32)   # dL_p/d(d^2) / P, read by the backward
+		check(L.find_contrastive_fwd(ptr(vecs), N, K, ptr(codes), codes.shape[1], ptr(pairs), P, float(margin), ptr(loss), ptr(coef),
+									 current_stream(vecs.device)), 'find_contrastive_fwd')
+		ctx.save_for_backward(vecs, pairs, coef)
+		return loss
+
+	@staticmethod
+	def backward(ctx, g):
+		L = _lib.lib()
+		vecs, pairs, coef = ctx.saved_tensors
+		N, K = vecs.shape
+		d = torch.empty_like(vecs)
+		check(L.find_contrastive_bwd(ptr(vecs), N, K, ptr(pairs), pairs.shape[0], ptr(coef), ptr(_c(g)), ptr(d),
+									 current_stream(vecs.device)), 'find_contrastive_bwd')
+		return d, None, None, None
+
+
+def contrastive_pose(vecs, codes, pairs, margin=0.5):
+	"""Mean contrastive loss of the pose vectors vecs (N, K) over the pairs (P, 2) (device int32, e.g. find_amd.losses.draw_pairs):
+	y = <codes_a, codes_b>, d = ||v_a - v_b||, L = y d^2 + (1 - y) max(margin - d^2, 0)^2 (reference losses.py:313-319).  codes (N, C)
+	are passed as fp32 (pose codes are -1 / 0 / 1: exact); the per-pair terms are combined in double and the loss rounded once."""
+	return _ContrastivePose.apply(vecs, codes, pairs, margin)
+
+
 class _Register(torch.autograd.Function):
 	"""X = ((verts + disp) * S) @ R(euler XYZ) + t     (model.py:481-491)."""
 

@@ -14,12 +14,13 @@ Constraints (checked or documented): every batch of one shape signature shares a
 (find_amd.optim.Adam(capturable=True), find_amd.optim.SGD); flags that make ModelWithLoss.forward read device values on the host
 (opts.restrict_3d_n_train) cannot be captured.  The warm-up iterations that precede a capture are DRY: parameters and optimiser
 state are put back before the capture, so N calls are N training steps, the first batch of a shape included (only the random
-generators -- the sampler's device generator, numpy's for the camera poses -- have advanced)."""
+generators -- the sampler's device generator, numpy's for the contrastive term's pairs and the camera poses -- have advanced)."""
 import collections
 
 import torch
 
 from . import functional as FN
+from . import losses as _losses
 
 from .structures import Meshes, TexturesUV, TexturesVertex
 
@@ -133,6 +134,12 @@ class GraphedStep:
 		self._draw_views = bool(self.flags.get('render_foot')) and self.flags.get('views') is None
 		if self.flags.get('views') is not None and not all(torch.is_tensor(t) and t.is_cuda for t in self.flags['views']):
 			raise RuntimeError('GraphedStep: views=(R, T) must be device tensors (a host tensor would be copied from pageable memory inside the capture)')
+		# The contrastive pose term's pairs (numpy's global generator too, drawn BEFORE the camera poses, model.py:1042-1071): a static input
+		# in the same way -- drawn per call in _load() ahead of the poses, or the caller's own device tensor.  P is fixed by the batch size,
+		# which the shape signature keys.
+		self._draw_pairs = bool(self.flags.get('cont_pose')) and self.flags.get('cont_pairs') is None
+		if self.flags.get('cont_pairs') is not None and not (torch.is_tensor(self.flags['cont_pairs']) and self.flags['cont_pairs'].is_cuda):
+			raise RuntimeError('GraphedStep: cont_pairs must be a device tensor (a host tensor would be copied from pageable memory inside the capture)')
 		m = model_with_loss.model
 		if latent_vectors is None:
 			latent_vectors = m.latent_vectors_train if self.flags.get('is_train', True) else m.latent_vectors_val
@@ -200,6 +207,14 @@ class GraphedStep:
 		st.idx_host = torch.zeros(max(n_lab, 1), bsz, dtype=torch.int64).pin_memory()
 		st.idx_dev = torch.zeros(max(n_lab, 1), bsz, dtype=torch.int64, device=dev)
 		flags = dict(self.flags)
+		st.pairs_host = st.pairs_dev = None
+		n_pose = batch['pose_code'].shape[0] if 'pose_code' in batch else 0
+		if self._draw_pairs and n_pose > 1:   # (one scan: no term, no draw -- as the eager step)
+			st.pairs_n = n_pose
+			st.pairs_host = torch.from_numpy(_losses.draw_pairs(n_pose)).pin_memory()
+			st.pairs_dev = st.pairs_host.to(dev)
+			flags['cont_pairs'] = st.pairs_dev
+			st.pairs_fresh = True   # the pairs just drawn serve the first step
 		st.views_host = st.views_dev = None
 		if self._draw_views:
 			R, T = self.mwl._views(self.opts)
@@ -237,6 +252,8 @@ class GraphedStep:
 			return loss, losses
 
 		self._load(st, batch)
+		if st.pairs_host is not None:
+			st.pairs_fresh = True   # (as the poses below)
 		if st.views_host is not None:
 			st.views_fresh = True   # (that _load consumed the flag without drawing: the captured poses serve the first REPLAY, so N calls make N draws -- ADVICE r3)
 		snap = self._snapshot()
@@ -327,6 +344,17 @@ class GraphedStep:
 		if getattr(st, 'hyper', None) is not None and st.hyper != self._hyper():
 			raise RuntimeError('GraphedStep: an optimiser hyper-parameter (lr, betas, ...) changed after the capture; they are launch arguments '
 							   'frozen into the graph -- build a new GraphedStep (FIND trains with constant rates, train.py:161-168)')
+		if st.pairs_host is not None:   # (before the poses: the reference's draw order)
+			if st.pairs_fresh:
+				st.pairs_fresh = False
+			else:
+				p = torch.from_numpy(_losses.draw_pairs(st.pairs_n))
+				if getattr(st, 'pairs_event', None) is not None:
+					st.pairs_event.synchronize()
+				st.pairs_host.copy_(p)
+				st.pairs_dev.copy_(st.pairs_host, non_blocking=True)
+				st.pairs_event = torch.cuda.Event()
+				st.pairs_event.record()
 		if st.views_host is not None:
 			if st.views_fresh:
 				st.views_fresh = False

@@ -2,8 +2,11 @@
 names and forward signatures); the arithmetic runs in libfind_hip.so through find_amd.functional.
 
 In scope: TextureLossGTSpace, DisplacementLoss (Chamfer, incl. the z-cut-off variants),
-MeshSmoothnessLoss, SilhouetteLoss.  Perceptual / Restyle / Contrastive losses need absent network weights or
+MeshSmoothnessLoss, SilhouetteLoss, ContrastiveLoss.  Perceptual / Restyle losses need absent network weights or
 submodules and are out of scope."""
+import itertools
+
+import numpy as np
 import torch
 
 from . import functional as FN
@@ -108,3 +111,41 @@ class SilhouetteLoss(nn.Module):
 	def forward(self, pred, gt):
 		"""MSE of the soft silhouettes (reference losses.py:122-128: nn.MSELoss), one pass each way in find_image_mse_*."""
 		return FN.image_mse(pred, gt)
+
+
+def draw_pairs(N, npairs=10):
+	"""The pairs ContrastiveLoss.forward draws (reference losses.py:326-331), with the same numpy calls on numpy's global generator --
+	same pairs, same generator state afterwards: min(npairs, N(N-1)/2) ORDERED pairs of distinct rows, (P, 2) int32 on the host."""
+	max_pairs = (N * (N - 1)) // 2
+	npairs = min(npairs, max_pairs)
+	all_pairs = list(itertools.permutations(np.arange(N), 2))
+	np.random.shuffle(all_pairs)
+	return np.array(all_pairs[:npairs], dtype=np.int32).reshape(-1, 2)
+
+
+def pairs_to_device(pairs, device):
+	"""Host (P, 2) pairs -> device int32, through pinned memory (no wait for the queue to drain)."""
+	t = torch.from_numpy(np.ascontiguousarray(pairs, dtype=np.int32))
+	if torch.device(device).type != 'cuda':
+		return t
+	return t.pin_memory().to(device, non_blocking=True)
+
+
+class ContrastiveLoss(nn.Module):
+	"""Contrastive loss of pose vectors against pose codes (reference losses.py:305-333), one HIP launch each way (functional.contrastive_pose)."""
+
+	def crit(self, vec1, vec2, code1, code2, margin=0.5):
+		"""L = y d^2 + (1 - y) max(margin - d^2, 0)^2 for one pair, y = <code1, code2>, d = ||vec1 - vec2|| (losses.py:307-319)."""
+		vecs = torch.stack([vec1, vec2])
+		codes = torch.stack([code1, code2]).to(device=vecs.device, dtype=torch.float32)
+		return FN.contrastive_pose(vecs, codes, pairs_to_device(np.array([[0, 1]]), vecs.device), margin)
+
+	def forward(self, vecs, codes, npairs=10, pairs=None):
+		"""Mean loss over min(npairs, N(N-1)/2) random ordered pairs of the N rows of vecs (N, K) / codes (N, C) (losses.py:321-333).
+		pairs (not in the reference): a device int32 (P, 2) tensor of pairs already drawn -- no draw here (the captured step's static input,
+		find_amd.graph).  Codes go to the kernel as fp32 (pose codes are -1 / 0 / 1: exact); the loss is fp32 (upstream's is float64,
+		DESIGN 7.1)."""
+		N = vecs.shape[0]
+		if pairs is None:
+			pairs = pairs_to_device(draw_pairs(N, npairs), vecs.device)
+		return FN.contrastive_pose(vecs, torch.as_tensor(codes).to(device=vecs.device, dtype=torch.float32), pairs)

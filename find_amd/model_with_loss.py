@@ -13,7 +13,7 @@ import torch
 
 from . import functional as FN
 from . import losses as _losses
-from .losses import DisplacementLoss, MeshSmoothnessLoss, SilhouetteLoss, TextureLossGTSpace
+from .losses import ContrastiveLoss, DisplacementLoss, MeshSmoothnessLoss, SilhouetteLoss, TextureLossGTSpace
 from .model import NeuralDisplacementField, PCAModel
 from .renderer import FootRenderer
 
@@ -22,11 +22,10 @@ nn = torch.nn
 model_zoo = dict(neural=NeuralDisplacementField, pca=PCAModel)
 
 OUT_OF_SCOPE_FLAGS = {
-	'vgg_perc': 'perceptual / restyle / contrastive losses are out of scope (SURVEY.md §2 #4)',
-	'restyle_perc_lat': 'perceptual / restyle / contrastive losses are out of scope (SURVEY.md §2 #4)',
-	'restyle_perc_feat': 'perceptual / restyle / contrastive losses are out of scope (SURVEY.md §2 #4)',
-	'restyle_perc_cluster': 'perceptual / restyle / contrastive losses are out of scope (SURVEY.md §2 #4)',
-	'cont_pose': 'perceptual / restyle / contrastive losses are out of scope (SURVEY.md §2 #4)',
+	'vgg_perc': 'perceptual / restyle losses are out of scope (SURVEY.md §2 #4)',
+	'restyle_perc_lat': 'perceptual / restyle losses are out of scope (SURVEY.md §2 #4)',
+	'restyle_perc_feat': 'perceptual / restyle losses are out of scope (SURVEY.md §2 #4)',
+	'restyle_perc_cluster': 'perceptual / restyle losses are out of scope (SURVEY.md §2 #4)',
 	'mask_out_pred_faces': 'mask_out_pred_faces belongs to the VertexFeatures model (out of scope)',
 }
 
@@ -36,6 +35,7 @@ TERMS = (
 	Term('chamf', 'loss_chamf', 'weight_chamf', True, False, '_raw_chamf'),
 	Term('smooth', 'loss_smooth', 'weight_smooth', True, False, '_raw_smooth'),
 	Term('texture', 'loss_tex', 'weight_tex', True, False, '_raw_texture'),
+	Term('cont_pose', 'loss_cont_pose', 'weight_cont_pose', False, False, '_raw_cont_pose'),
 	Term('pix', 'loss_pix', 'weight_pix', False, True, '_raw_pix'),
 	Term('sil', 'loss_sil', 'weight_sil', False, True, '_raw_sil'),
 )
@@ -141,7 +141,7 @@ def model_from_opts(opts):
 
 class _Step:
 	"""What one forward() call has at hand while the registry is walked."""
-	__slots__ = ('batch', 'epoch', 'opts', 'res', 'is_train', 'use_z_cutoff', 'gt_z_cutoff', 'pred', 'gt', 'gt_chamf', 'gt_tex')
+	__slots__ = ('batch', 'epoch', 'opts', 'res', 'is_train', 'use_z_cutoff', 'gt_z_cutoff', 'pred', 'gt', 'gt_chamf', 'gt_tex', 'cont_pairs')
 
 
 class ModelWithLoss(nn.Module):
@@ -161,6 +161,7 @@ class ModelWithLoss(nn.Module):
 		self.templ_smooth_loss = MeshSmoothnessLoss()
 		self.pix_loss = nn.MSELoss()      # (attributes of the reference; the forward computes both losses through find_image_mse_*)
 		self.sil_loss = SilhouetteLoss()
+		self.contrastive_loss = ContrastiveLoss()
 		# (max_faces_per_bin only sizes PyTorch3D's coarse bins -- 30 000 for the full-resolution scans, model.py:987; no effect on results)
 		self.rdr = FootRenderer(image_size=256, device=device, bin_size=None, max_faces_per_bin=None if opts.low_poly_meshes else 30000)
 
@@ -176,6 +177,10 @@ class ModelWithLoss(nn.Module):
 		sfx = 'train' if st.is_train else 'val'
 		codes = {k: st.batch.get(f'{k}_{sfx}', None) for k in ('shapevec', 'texvec', 'posevec')}
 		return self.col_loss(self.model, st.batch, **codes, **(dict(gt_samples=st.gt_tex) if st.gt_tex is not None else {}))
+
+	def _raw_cont_pose(self, st):
+		# (pairs drawn at the top of forward(), before the camera poses: the reference's numpy order, model.py:1042-1071)
+		return self.contrastive_loss(st.batch['posevec_train' if st.is_train else 'posevec_val'], st.batch['pose_code'], pairs=st.cont_pairs)
 
 	def _raw_pix(self, st):
 		# images are compared inside the silhouettes only (model.py:1101-1105): MSE(image * mask, gt image * gt mask), one pass each way
@@ -248,9 +253,10 @@ class ModelWithLoss(nn.Module):
 	def forward(self, batch, epoch, opts, chamf=False, smooth=False, texture=False, pix=False, vgg_perc=False, sil=False,
 				restyle_perc_lat=False, restyle_perc_feat=False, restyle_perc_cluster=False, cont_pose=False, render_foot=False,
 				save_renders=False, render_dir='_pix', is_train=True, use_z_cutoff=False, gt_z_cutoff=None, restyle_feature_maps=None,
-				no_displacement=False, return_renders=False, copy_mask_out=True, mask_out_pred_faces=False, views=None):
+				no_displacement=False, return_renders=False, copy_mask_out=True, mask_out_pred_faces=False, views=None,
+				cont_pairs=None):
 		given = dict(vgg_perc=vgg_perc, restyle_perc_lat=restyle_perc_lat, restyle_perc_feat=restyle_perc_feat, restyle_perc_cluster=restyle_perc_cluster,
-					 cont_pose=cont_pose, mask_out_pred_faces=mask_out_pred_faces)
+					 mask_out_pred_faces=mask_out_pred_faces)
 		for name, why in OUT_OF_SCOPE_FLAGS.items():
 			if given[name]:
 				raise NotImplementedError(why)
@@ -258,9 +264,21 @@ class ModelWithLoss(nn.Module):
 			# (upstream ends in an AttributeError inside TextureLossGTSpace, losses.py:22-57)
 			raise NotImplementedError('texture=True: the texture loss queries the model\'s colour field, and the PCA model (model_type=\'pca\') has '
 									  'none; switch the texture term off for it')
-		enabled = dict(chamf=chamf, smooth=smooth, texture=texture, pix=pix, sil=sil)
+		# The contrastive pose term (model.py:1042-1049): a batch without pose rows is an error whatever its size; one scan gives no term.
+		# Its pairs are drawn HERE, before anything else draws from numpy's global generator: upstream shuffles them before sampling the
+		# camera poses (model.py:1060-1071).  cont_pairs (not in the reference): device int32 (P, 2) pairs already drawn -- the captured
+		# step's static input (find_amd.graph), like views=.
+		pairs = None
+		if cont_pose:
+			pvec = 'posevec_train' if is_train else 'posevec_val'
+			if pvec not in batch:
+				raise ValueError("Contrastive pose loss used, but no pose found")
+			if batch['pose_code'].shape[0] > 1:
+				pairs = cont_pairs if cont_pairs is not None else _losses.pairs_to_device(_losses.draw_pairs(batch['pose_code'].shape[0]), batch[pvec].device)
+		enabled = dict(chamf=chamf, smooth=smooth, texture=texture, cont_pose=pairs is not None, pix=pix, sil=sil)
 
 		st = _Step()
+		st.cont_pairs = pairs
 		st.batch, st.epoch, st.opts, st.is_train = batch, epoch, opts, is_train
 		st.use_z_cutoff, st.gt_z_cutoff = use_z_cutoff, gt_z_cutoff
 		# train_network asks for renders whenever a checkpoint is saved (train.py:58-66: save_renders at epoch 0, every *_save_every epochs

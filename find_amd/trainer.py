@@ -119,7 +119,7 @@ class Trainer:
 			return 'opts.step_per_epoch accumulates gradients over the epoch'
 		if getattr(o, 'restrict_3d_n_train', None) is not None or getattr(o, 'restrict_3d_train_key', None) is not None:
 			return 'per-scan 3-D supervision switches are read on the host'
-		if not any(model_kwargs.get(k) for k in ('chamf', 'smooth', 'texture', 'pix', 'sil')):
+		if not any(model_kwargs.get(k) for k in ('chamf', 'smooth', 'texture', 'cont_pose', 'pix', 'sil')):
 			return 'no loss term enabled'
 		for op in optims:
 			if not isinstance(op, (optim.Adam, optim.SGD)):

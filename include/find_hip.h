@@ -260,6 +260,20 @@ int find_weighted_terms_fwd(int64_t n, const float* const* terms, const float* w
 int find_weighted_terms_bwd(int64_t n, const float* weights, const float* g_total, const float* g_scaled, float* d_terms, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Contrastive pose loss.  Replaces ContrastiveLoss.forward / crit (src/model/losses.py:305-333; call site ModelWithLoss.forward,
+ * src/model/model.py:1042-1049): for P drawn pairs (a, b) -- pairs (P, 2) int32, drawn on the host --
+ *   y = <codes[a], codes[b]>, d2 = ||vecs[a] - vecs[b]||^2, L = y d2 + (1 - y) max(margin - d2, 0)^2, *loss_out = sum_p L_p / P.
+ * vecs (N, K) fp32, codes (N, C) fp32; N >= 2, 1 <= P <= N(N-1).  One workgroup; the per-pair terms are formed in double and summed in
+ * pair order (deterministic, no atomics), the loss rounded to fp32 once.  coef_ws (P floats) receives dL_p/d(d2) / P for the backward.
+ * Backward: d_vecs (N, K) is overwritten with *d_loss * dloss/dvecs (d_loss: device scalar), every element owned by one thread that
+ * walks the pairs in order; d = 0 gives a zero gradient.  A pair index outside [0, N) yields NaN (loss, coef, every gradient entry).
+ * ---------------------------------------------------------------------------------------------- */
+int find_contrastive_fwd(const float* vecs, int64_t N, int64_t K, const float* codes, int64_t C, const int32_t* pairs, int64_t P, float margin,
+						 float* loss_out, float* coef_ws, void* stream);
+int find_contrastive_bwd(const float* vecs, int64_t N, int64_t K, const int32_t* pairs, int64_t P, const float* coef_ws, const float* d_loss,
+						 float* d_vecs, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Similarity registration  X = ((v + disp) * S) @ R(euler 'XYZ') + t.
  * Replaces euler_angles_to_matrix + Transform3d().scale().rotate().translate().transform_points
  * in NeuralDisplacementField.get_meshes (src/model/model.py:481-491).
