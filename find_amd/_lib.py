@@ -1,16 +1,11 @@
 """ctypes binding of libfind_hip.so (include/find_hip.h).  There is NO fallback: if the HIP library is
-missing or a call fails, a RuntimeError is raised.
-
-FIND_DIAG=1 in the environment loads libfind_hip_diag.so instead -- the laboratory build of the same sources (include/find_hip_diag.h:
-fault reproducers, superseded kernels, timers, wrong-result ablation bits).  Only tools/ do that; tests, bench.py and
-__graft_entry__ run the product."""
+missing or a call fails, a RuntimeError is raised."""
 import ctypes
 import os
 from ctypes import POINTER, Structure, c_char_p, c_float, c_int, c_int16, c_int32, c_int64, c_void_p
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
-DIAG = os.environ.get('FIND_DIAG', '0') not in ('', '0')
-LIB_PATH = os.path.join(_PKG, 'lib', 'libfind_hip_diag.so' if DIAG else 'libfind_hip.so')
+LIB_PATH = os.path.join(_PKG, 'lib', 'libfind_hip.so')
 MAX_LAYERS = 8
 ABI_VERSION = 2
 
@@ -125,10 +120,6 @@ PROTOTYPES = {
 	'find_render_features_bwd': (c_int, [POINTER(RenderParams), _P, _P, _I, _P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _I, _P, _I, _P]),
 	'find_points_render': (c_int, [POINTER(PointsParams), _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
 }
-# include/find_hip_diag.h: what libfind_hip_diag.so exports on top
-DIAG_PROTOTYPES = {
-	'find_debug_raster_ablate': (c_int, [_I]),
-}
 
 
 def lib():
@@ -144,7 +135,7 @@ def lib():
 	# process ends up with device pointers of one runtime handed to the other and every launch fails ("no ROCm-capable device").
 	import torch  # noqa: F401
 	L = ctypes.CDLL(LIB_PATH)
-	for name, (res, args) in list(PROTOTYPES.items()) + (list(DIAG_PROTOTYPES.items()) if DIAG else []):
+	for name, (res, args) in PROTOTYPES.items():
 		try:
 			fn = getattr(L, name)
 		except AttributeError as e:
@@ -215,12 +206,8 @@ def set_tuning(key, value, device=None):
 
 
 def _raster_switches(L, bits):
-	"""The process-wide switches of the rasteriser / the Chamfer search: the product takes the result-preserving bits (find_render_switches)
-	and refuses the rest; the laboratory build takes every bit (find_debug_raster_ablate)."""
-	if DIAG:
-		check(L.find_debug_raster_ablate(bits), 'find_debug_raster_ablate')
-	else:
-		check(L.find_render_switches(bits), 'find_render_switches')
+	"""The process-wide switches of the rasteriser / the Chamfer search: the result-preserving bits (find_render_switches); the rest is refused."""
+	check(L.find_render_switches(bits), 'find_render_switches')
 
 
 def get_tuning(key, device=None):

@@ -1,6 +1,4 @@
-"""Build the two libraries (gfx950) in-tree with hipcc: libfind_hip.so, the product, and libfind_hip_diag.so, the same sources with -DFIND_DIAG
-(fault reproducers, superseded A/B kernels, timers, wrong-result ablation bits: include/find_hip_diag.h) for tools/.
-`python -m find_amd.build [-j N] [--force] [--no-diag]`."""
+"""Build libfind_hip.so (gfx950) in-tree with hipcc.  `python -m find_amd.build [-j N] [--force]`."""
 import os
 import subprocess
 import sys
@@ -12,9 +10,7 @@ CSRC = os.path.join(PKG, 'csrc')
 INCLUDE = os.path.join(ROOT, 'include')
 LIBDIR = os.path.join(PKG, 'lib')
 LIB = os.path.join(LIBDIR, 'libfind_hip.so')
-LIB_DIAG = os.path.join(LIBDIR, 'libfind_hip_diag.so')
 OBJDIR = os.path.join(LIBDIR, 'obj')
-OBJDIR_DIAG = os.path.join(LIBDIR, 'obj_diag')
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-I' + INCLUDE, '-I' + CSRC] + os.environ.get('FIND_EXTRA_HIPCC_FLAGS', '').split()
 
@@ -32,16 +28,9 @@ def _deps_mtime():
 LAST_COMPILED = []   # objects the last build() call compiled (what a caller may report: __graft_entry__.build)
 
 
-def build(force=False, jobs=4, verbose=True, diag=True):
-	"""Compile every csrc/*.hip for gfx950 and link libfind_hip.so (and, with diag, libfind_hip_diag.so).  Incremental on mtimes."""
+def build(force=False, jobs=4, verbose=True):
+	"""Compile every csrc/*.hip for gfx950 and link libfind_hip.so.  Incremental on mtimes."""
 	del LAST_COMPILED[:]
-	lib = _build_one(LIB, OBJDIR, [], force, jobs, verbose)
-	if diag:
-		_build_one(LIB_DIAG, OBJDIR_DIAG, ['-DFIND_DIAG'], force, jobs, verbose)
-	return lib
-
-
-def _build_one(LIB, OBJDIR, extra, force, jobs, verbose):
 	os.makedirs(OBJDIR, exist_ok=True)
 	hdr_m = _deps_mtime()
 	todo, objs = [], []
@@ -53,7 +42,7 @@ def _build_one(LIB, OBJDIR, extra, force, jobs, verbose):
 
 	def cc(job):
 		src, obj = job
-		cmd = [HIPCC] + FLAGS + extra + ['-c', src, '-o', obj]
+		cmd = [HIPCC] + FLAGS + ['-c', src, '-o', obj]
 		if verbose:
 			print('[find_amd.build]', ' '.join(cmd), flush=True)
 		r = subprocess.run(cmd, capture_output=True, text=True)
@@ -78,4 +67,4 @@ if __name__ == '__main__':
 	j = 4
 	if '-j' in sys.argv:
 		j = int(sys.argv[sys.argv.index('-j') + 1])
-	print(build(force='--force' in sys.argv, jobs=j, diag='--no-diag' not in sys.argv))
+	print(build(force='--force' in sys.argv, jobs=j))

@@ -1080,8 +1080,7 @@ struct ChamferWs {
 // 16 x 10000 x 10000: 0.18 against 0.50 ms).  But the training step runs its Chamfer term BESIDE the texture pass's MLP chain (a second
 // stream, model_with_loss.py), and there the grid's dependent, scattered loads fare badly -- 430 us instead of the brute-force kernel's
 // 134 us of packed arithmetic, the step 2.4 - 2.6 instead of 2.19 ms -- so the 5000-sample training clouds stay with all pairs and the
-// grid serves the evaluation sizes (eval_3d.py:148: 10 000 samples).  Bits of the profiling switch (find_debug_raster_ablate): 512 = never
-// the grid, 1024 = the grid from 64 points on (tests).
+// grid serves the evaluation sizes (eval_3d.py:148: 10 000 samples).  Bits of find_render_switches: 512 = never the grid, 1024 = the grid from 64 points on (tests).
 constexpr int64_t GRID_MIN_POINTS = 8192;
 static void carve_chamfer(int64_t n, int64_t p1_max, int64_t p2_max, void* ws, ChamferWs* o) {
 	Carver c(ws);

@@ -128,7 +128,7 @@ static void carve_fwd(const find_mlp_params* p, const Dims& d, bool save, void* 
 
 // Per-device state of the MLP entry points (find_hip.h: find_ctx_create).  Nothing below is process-global.
 enum { K_GEMM2_PE = 0, K_GEMM3_RELU, K_GEMM3_MASK, K_GEMM3_NONE, K_GEMM4_4_RELU, K_GEMM4_4_MASK, K_GEMM4_4_NONE, K_GEMM4_2_RELU, K_GEMM4_2_MASK,
-	   K_GEMM4_2_NONE, K_GEMM5_RELU, K_GEMM5_MASK, K_GEMM5_NONE, K_GEMM6_RELU, K_GEMM6_MASK, K_GEMM6_NONE, K_GEMM7_RELU, K_GEMM7_MASK, K_GEMM7_NONE, K_DW2, K_DW3, K_DW6, K_DW6G, K_FUSED, K_FUSED2, K_FUSED6, K_FUSED6_2, K_DW2G, K_REDUCE, K_DW2_REPRO, K_GEMM5_RELU_H, K_GEMM5_MASK_H, K_DW3_H, K_GEMM5_RELU_V, K_GEMM5_MASK_V, K_DW3_V, K_GEMM7_RELU_V, K_GEMM7_MASK_V, K_DW6_V, K_GEMM7_MASK_VF, K_COUNT };
+	   K_GEMM4_2_NONE, K_GEMM5_RELU, K_GEMM5_MASK, K_GEMM5_NONE, K_GEMM7_RELU, K_GEMM7_MASK, K_GEMM7_NONE, K_DW2, K_DW3, K_DW6, K_DW6G, K_FUSED, K_FUSED2, K_FUSED6, K_FUSED6_2, K_DW2G, K_REDUCE, K_GEMM5_RELU_H, K_GEMM5_MASK_H, K_DW3_H, K_GEMM5_RELU_V, K_GEMM5_MASK_V, K_DW3_V, K_GEMM7_RELU_V, K_GEMM7_MASK_V, K_DW6_V, K_GEMM7_MASK_VF, K_COUNT };
 constexpr int N_SIDE = 4;       // internal streams: 0 = q (large head layers' dW), 1 / 2 = first head layers + trunk layers, 3 = slab reduces
 constexpr int N_EVENTS = 512;   // event ring: an MLP call with 3 x 8 layers uses ~170; checked per call
 
@@ -137,66 +137,46 @@ struct find_ctx {
 	int num_cus = 256;
 	int lds_bytes = 160 * 1024;   // largest dynamic LDS one workgroup may ask for on this device
 	// knobs (find_hip.h: find_ctx_set)
-	int ablate = 0;               // switches; the product accepts MLP_SWITCHES only (common.h), the diagnostics build every bit
-	int x3_abl = 0;               // diagnostics build: ablation variant of gemm6 / gemm7 (tools/ablate_x3.py)
-	unsigned long long* dbg = nullptr;
-	unsigned long long* dw2_verify = nullptr;   // diagnosis (tools/probe_lds_fault.py): log buffer of dw2_kernel's stage verification
+	int ablate = 0;               // result-preserving switches (MLP_SWITCHES, common.h)
 	int64_t gemm4_min_units = 1024;
 	int gemm4_small = 64;         // column-quarter gemm4 for launches of at least this many 32-row units (0: never)
-	int dw_pe_target = 256;       // workgroups of the Fourier layer's weight-gradient launch (one round over the chip)
-	int dw_pe_lds_free = 1;       // Fourier layer's weight gradient: 1 = dwpe_kernel (no LDS, one frequency per lane), 0 = dw_kernel<AMODE_PE> (round 1, LDS-staged)
+	int gemm5_min_units = 1024;
+	int gemm6_min_units = 1024;
+	int mlp_f16 = 0;              // default precision of calls that do not name one
+	int fused_max_units = 512;    // chains of layers over at most this many 32-row tiles run as ONE fused_chain_kernel launch (0: never)
+	int fused6 = 1;               // bf16x3 calls run their chains on fused6_kernel (0: the fp32-MFMA chain, as the other precisions)
 	int dw2_min_cps = 8;          // at least this many 16-row chunks per dw2 workgroup (4: 2.257, 8: 2.243, 12: 2.266 ms/step at C2)
+	int dw_lds_free = 1;          // 256 x 256 weight gradients: 1 = dw4_kernel (no LDS, <= 256 registers), 0 = dw2_kernel (LDS-DMA ring, whole register file claimed)
+	int lds_exclusive = 0;        // 1 = the LDS-DMA ring kernels reserve the whole LDS of their CU: round 1's containment of the co-residence fault, which
+	                              // round 2 showed to be about registers, not LDS (see "Co-residence" below); off by default now
+	int reduce_exclusive = 0;     // diagnosis only: 1 = the slab reduce (16 KB of LDS) reserves its CU's whole LDS; 2 = LDS-free, slow reduce: the stress
+	                              // configuration for the co-residence fault (long-lived foreign waves beside the weight-gradient kernels)
 	int bwd_streams = 1;          // weight gradients on the side streams
 	int fwd_streams = 1;          // colour head on a side stream beside the displacement head
 	int reduce_stream = 0;        // 1 = slab reduces of the large head layers on their own stream R (two alternating slab sets): what the LDS-ring weight
 	                              // gradient needed (its reduce only got a CU when a ring workgroup retired); with dw4_kernel the reduce behind its
 	                              // launch on Q is 0.6 - 0.9 % faster (train_3d 3.245 -> 3.225 ms, C2 2.220 -> 2.199), so off by default
-	int gemm5_min_units = 1024;
-	int gemm6_min_units = 1024;
-	int gemm7 = 1;                // bf16x3 Linear kernel: 1 = gemm7 (W in registers, activations through LDS), 0 = gemm6 (W planes in LDS; kept for A/B)
-	int dwpe6 = 1;                // knob: the Fourier layer's weight gradient of bf16x3 calls on dwpe6_kernel (0: dwpe_kernel, fp32 MFMA)
-	int dw6_group = 1;            // knob: grouped weight gradients of bf16x3 calls on dw6_group_kernel (0: dw4_group, fp32 MFMA)
-	int direct_w = 1;             // knob: bf16x3 kernels read the model's weights themselves (transposed / Fourier order) instead of repacked copies (0: A/B)
-	int mlp_f16 = 0;              // default precision of calls that do not name one
-	int lds_exclusive = 0;        // 1 = the LDS-DMA ring kernels reserve the whole LDS of their CU: round 1's containment of the co-residence fault, which
-	                              // round 2 showed to be about registers, not LDS (see "Co-residence" below); off by default now
-	int reduce_exclusive = 0;     // diagnosis only: 1 = the slab reduce (16 KB of LDS) reserves its CU's whole LDS; 2 = LDS-free, slow reduce: the stress
-	                              // configuration for the co-residence fault (long-lived foreign waves beside the weight-gradient kernels)
-	int dw_lds_free = 1;          // 256 x 256 weight gradients: 1 = dw4_kernel (no LDS, <= 256 registers), 0 = dw2_kernel (LDS-DMA ring, whole register file claimed);
-	                              // reproducers of the co-residence fault: 2 = dw4_wide_kernel (no LDS, 328 registers), 3 = dw2_repro_kernel (312 registers)
-	int group_spf = 0;            // grouped weight gradients: splits per foot (0 = cost model of group_geometry)
-	int fused_max_units = 512;    // chains of layers over at most this many 32-row tiles run as ONE fused_chain_kernel launch (0: never)
-	int dw6_wgs = 0;              // knob: workgroups (= slabs) of a dw6 launch; 0 = one per CU, half that beside the dX chain (weight_grad)
-	int fused6 = 1;               // knob: bf16x3 calls run their chains on fused6_kernel (0: the fp32-MFMA chain, as the other precisions)
+	int bind_streams = 1;         // 0 = keep the side streams as created
+	int defer_join = 0;           // read by the next find_mlp_bwd: leave the weight-gradient side streams running behind the call (find_hip.h)
+	int act16 = 1;                // in the opt-in fp16 mode the heads' hidden activations and their gradients are STORED as fp16 at the large
+	                              // shared-template shapes (use_act16): those layers are HBM-bound, and the matrix pipe rounds them to fp16 anyway
+	int bcast_fold = 1;           // inside act16 the broadcast first head layer's output is formed by its readers instead of stored (use_fold)
+	int footsum_fold = 1;         // the foot sums of a shared template's first-layer dZ are formed inside the dX GEMM that produces it (mlp_gemm7.h FSUM)
 	// internal streams / events
 	hipStream_t side[N_SIDE] = {nullptr, nullptr, nullptr, nullptr};
 	bool side_bound = false;      // the side streams have been chosen against the hardware queue of a caller's stream (bind_side_streams)
-	int bind_streams = 1;         // knob: 0 = keep the side streams as created
-	int r_queue = 2;              // knob: the side stream (0 = Q, 1 = T1, 2 = T2) whose hardware queue the slab-reduce stream R shares
-	int cu_reserve = 0;           // knob: CUs per XCD the side streams may NOT use (hipExtStreamCreateWithCUMask): the short kernels on the caller's
-	                              // stream -- the loss-side chain the main backward waits for -- then always find a free CU beside the side streams'
-	                              // long weight-gradient workgroups.  Takes effect when the side streams are bound (first fork).  Masked streams are
-	                              // BLOCKING streams (HIP offers no other kind with a mask): only for callers on a non-default stream
-	int side_cus = 256;           // CUs a side stream may use (num_cus - 8 cu_reserve once bound): what the weight-gradient launches are sized for
 	hipEvent_t ev[N_EVENTS];
 	int n_events = 0;
 	int next = 0;
 	int events_per_call_max = 0;
+	hipEvent_t pend_ev[N_SIDE] = {nullptr, nullptr, nullptr, nullptr};   // end of the deferred work on each side stream
+	bool pend[N_SIDE] = {};       // side stream k carries deferred work nobody has waited for yet
 	bool attr_done[K_COUNT] = {};
 	// how the last forward calls that saved a workspace stored the heads' activations (act16): the backward of a workspace follows its
 	// forward's decision even if a knob was turned in between (ring of the last 16; a workspace not found falls back to the rule)
 	struct Act16Note { const void* ws; bool a16; bool fold; };
 	Act16Note act16_notes[16] = {};
 	int act16_next = 0;
-	int pe_on_t2 = 1;             // knob: the Fourier layer's weight gradient of a shared-template backward runs on T2 instead of behind dw6 on Q
-	int footsum_fold = 1;         // knob: the foot sums of a shared template's first-layer dZ are formed inside the dX GEMM that produces it (mlp_gemm7.h FSUM)
-	int group_head0 = 1;          // knob: a shared template's first head layers' weight gradients ride in the trunk's grouped launch (mlp_bwd_body)
-	int bcast_fold = 1;           // knob: inside act16 the broadcast first head layer's output is formed by its readers instead of stored (use_fold)
-	int act16 = 1;                // knob: in the opt-in fp16 mode the heads' hidden activations and their gradients are STORED as fp16 at the large
-	                              // shared-template shapes (use_act16): those layers are HBM-bound, and the matrix pipe rounds them to fp16 anyway
-	int defer_join = 0;           // knob, read by the next find_mlp_bwd: leave the weight-gradient side streams running behind the call (find_hip.h)
-	hipEvent_t pend_ev[N_SIDE] = {nullptr, nullptr, nullptr, nullptr};   // end of the deferred work on each side stream
-	bool pend[N_SIDE] = {};       // side stream k carries deferred work nobody has waited for yet
 	// set per call
 	bool f16 = false;
 	bool x3 = false;              // this call runs its 256 -> 256 layers as bf16x3 (fp32-faithful on the bf16 matrix pipe, mlp_gemm6.h)
@@ -234,9 +214,9 @@ namespace mlp {
 //   * not the slabs (a private slab set per weight gradient: same rate); not the ring (every stage of every chunk equals HBM when it is
 //     published AND after the wave has consumed it, 2.35 M stages per run); not barrier timing, DMA in flight, M0 hazards, operand-register
 //     reuse, barrier flavour (each padded / changed: same rate).
-//   * not LDS at all: dw4_wide_kernel -- no LDS, no DMA, no barrier, dw2's tile shape read straight from global memory -- breaks the
+//   * not LDS at all: a four-wave dw4 ("dw4 wide") -- no LDS, no DMA, no barrier, dw2's tile shape read straight from global memory -- breaks the
 //     same way (663), while dw4_kernel, the same code with half the tile per wave, never does (0 in 1450 passes).
-//   * what the victims share is their REGISTER SHAPE: dw2 312, dw2_group 300, dw4_wide 328 registers per lane -- all 256 accumulator
+//   * what the victims share is their REGISTER SHAPE: dw2 312, dw2_group 300, dw4 wide 328 registers per lane -- all 256 accumulator
 //     registers (the whole AGPR set) behind fewer than 256 architectural ones, one wave per SIMD.  Every kernel with at most 256 registers
 //     was clean; so was the masked gemm3 when it still took 328 (200 architectural + 128 accumulator registers: 0 in 160 stress passes,
 //     rebuilt with -DFIND_GEMM3_MIN_WGS=1), so the trigger is narrower than "more than 256".  And dw2 UNCHANGED except for its allocation
@@ -249,7 +229,7 @@ namespace mlp {
 // 292-register victim ran clean: something else of the step's setting takes part).  The rule adopted, a superset of every shape that
 // broke and enforced by tests/test_host_api.py on the compiler's output: a kernel either fits in 256 registers or claims the whole file.  dw4_kernel (<= 256,
 // two waves per SIMD, no LDS) is the default weight gradient; dw2 / dw2_group / dw3 claim the file; gemm3 is capped at 256 through its
-// launch bounds; dw2_repro_kernel and dw4_wide_kernel stay as the reproducers ("dw_lds_free" = 3 / 2).  The whole-LDS reservation is
+// launch bounds (the two reproducers -- round 1's dw2 and the wide dw4 -- have been removed since).  The whole-LDS reservation is
 // off by default ("lds_exclusive"): the stress runs are clean without it, and what it really did was keep most neighbours away.
 template <typename K>
 static int prepare_kernel(find_ctx* c, int id, K kernel, int need_bytes, int* launch_bytes, bool reserve = true) {
@@ -424,30 +404,6 @@ static int launch_gemm5(find_ctx* c, int epi, const Gemm2Args& a, int64_t feet, 
 	return launch_gemm5_t<EPI_NONE>(c, a, feet, s);
 }
 
-#ifdef FIND_DIAG   // gemm6 (weight planes in LDS), superseded by gemm7: kept in the diagnostics build for A/B runs ("gemm7" = 0)
-template <int EPI>
-static int launch_gemm6_t(find_ctx* c, Gemm2Args a, int64_t feet, hipStream_t s) {
-	int lds = 0;
-	const int rc = prepare_kernel(c, K_GEMM6_RELU + (EPI == EPI_BIAS_RELU ? 0 : EPI == EPI_MASK ? 1 : 2), &gemm6_kernel<EPI>, GEMM6_LDS, &lds);
-	if (rc != FIND_OK) return rc;
-	a.tiles_per_foot = (int)cdiv(a.V, 32);
-	a.ntiles = (int)(a.tiles_per_foot * feet);
-	constexpr int G = 8 * (8 / G6_NI);  // the column groups of a row range sit 8 blocks apart (same XCD)
-	const int grid = std::max(G, (c->num_cus / G) * G);
-	if constexpr (EPI == EPI_BIAS_RELU) {
-		const int abl = c->x3_abl & 7;   // profiling only (tools/ablate_x3.py)
-		if (abl) {
-#define FIND_G6_ABL(N) case N: { FIND_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm6_kernel<EPI, N>), hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_bytes), "hipFuncSetAttribute"); \
-			hipLaunchKernelGGL((gemm6_kernel<EPI, N>), dim3(grid), dim3(GEMM6_NW * 64), lds, s, a); return FIND_OK; }
-			switch (abl) { FIND_G6_ABL(1) FIND_G6_ABL(2) FIND_G6_ABL(3) FIND_G6_ABL(4) FIND_G6_ABL(5) FIND_G6_ABL(6) FIND_G6_ABL(7) }
-#undef FIND_G6_ABL
-		}
-	}
-	hipLaunchKernelGGL((gemm6_kernel<EPI>), dim3(grid), dim3(GEMM6_NW * 64), lds, s, a);
-	return FIND_OK;
-}
-#endif
-
 template <int EPI>
 static int launch_gemm7_t(find_ctx* c, Gemm2Args a, int64_t feet, hipStream_t s) {
 	int lds = 0;
@@ -456,17 +412,6 @@ static int launch_gemm7_t(find_ctx* c, Gemm2Args a, int64_t feet, hipStream_t s)
 	a.tiles_per_foot = (int)cdiv(a.V, 32);
 	a.ntiles = (int)(a.tiles_per_foot * feet);
 	const int grid = std::max(16, (c->num_cus / 16) * 16);   // the two column halves of a row range sit 8 blocks apart (same XCD)
-#ifdef FIND_DIAG
-	if constexpr (EPI == EPI_BIAS_RELU) {
-		const int abl = c->x3_abl & 15;   // profiling only (tools/ablate_x3.py)
-		if (abl) {
-#define FIND_G7_ABL(N) case N: { FIND_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm7_kernel<EPI, N>), hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_bytes), "hipFuncSetAttribute"); \
-			hipLaunchKernelGGL((gemm7_kernel<EPI, N>), dim3(grid), dim3(GEMM7_NW * 64), lds, s, a); return FIND_OK; }
-			switch (abl) { FIND_G7_ABL(1) FIND_G7_ABL(2) FIND_G7_ABL(4) FIND_G7_ABL(8) FIND_G7_ABL(3) FIND_G7_ABL(7) FIND_G7_ABL(15) FIND_G7_ABL(12) FIND_G7_ABL(14) }
-#undef FIND_G7_ABL
-		}
-	}
-#endif
 	hipLaunchKernelGGL((gemm7_kernel<EPI>), dim3(grid), dim3(GEMM7_NW * 64), lds, s, a);
 	return FIND_OK;
 }
@@ -512,13 +457,6 @@ static int launch_gemm7(find_ctx* c, int epi, const Gemm2Args& a, int64_t feet, 
 	return launch_gemm7_t<EPI_NONE>(c, a, feet, s);
 }
 
-#ifdef FIND_DIAG
-static int launch_gemm6(find_ctx* c, int epi, const Gemm2Args& a, int64_t feet, hipStream_t s) {
-	if (epi == EPI_BIAS_RELU) return launch_gemm6_t<EPI_BIAS_RELU>(c, a, feet, s);
-	if (epi == EPI_MASK) return launch_gemm6_t<EPI_MASK>(c, a, feet, s);
-	return launch_gemm6_t<EPI_NONE>(c, a, feet, s);
-}
-#endif
 
 static int launch_gemm3(find_ctx* c, int epi, const Gemm2Args& a, int64_t feet, hipStream_t s) {
 	if (epi == EPI_BIAS_RELU) return launch_gemm3_t<64, EPI_BIAS_RELU>(c, a, feet, s);
@@ -539,7 +477,7 @@ static int launch_gemm(find_ctx* c, int amode, int epi, const GemmArgs& a, int64
 	b.pos = a.pos; b.pos_foot_stride = a.pos_foot_stride; b.Bm = a.Bm; b.pe = a.pe;
 	b.w0 = a.w0; b.w1 = a.w1; b.ldw = a.ldw; b.nchunk = a.nchunk; b.w_tr = a.w_tr;
 	b.bias = a.bias; b.bias_foot_stride = a.bias_foot_stride; b.mask = a.mask; b.mask_foot_stride = a.mask_foot_stride;
-	b.y = a.y; b.y_foot_stride = a.y_foot_stride; b.ldy = a.ldy; b.V = a.V; b.ablate = c->ablate; b.dbg = c->dbg;
+	b.y = a.y; b.y_foot_stride = a.y_foot_stride; b.ldy = a.ldy; b.V = a.V; b.ablate = c->ablate;
 	b.va_bias = a.va_bias; b.va_bias_stride = a.va_bias_stride; b.vm_bias = a.vm_bias; b.vm_bias_stride = a.vm_bias_stride;
 	b.fs_out = a.fs_out; b.fs_slot_stride = a.fs_slot_stride; b.cs_out = a.cs_out;
 	if (amode == AMODE_PE) return launch_gemm2_pe(c, b, feet, s);
@@ -548,9 +486,6 @@ static int launch_gemm(find_ctx* c, int amode, int epi, const GemmArgs& a, int64
 	// (gemm5 keeps the whole W per workgroup, so 216 units occupy 27 CUs: 22 us against 13 us for gemm4 on column quarters)
 	if (c->f16 && k256 && units >= c->gemm5_min_units) return launch_gemm5(c, epi, b, feet, s, a.h16 != 0);
 	FIND_REQUIRE(!a.h16, "launch_gemm: an fp16-stored layer reached a kernel that reads fp32 (act16 and the kernel selection disagree)");
-#ifdef FIND_DIAG
-	if (c->x3 && k256 && units >= c->gemm6_min_units && !c->gemm7) { FIND_REQUIRE(!a.va_bias && !a.vm_bias, "launch_gemm: gemm6 forms no virtual operand"); return launch_gemm6(c, epi, b, feet, s); }
-#endif
 	if (c->x3 && k256 && units >= c->gemm6_min_units) return launch_gemm7(c, epi, b, feet, s);
 	FIND_REQUIRE(!a.va_bias && !a.vm_bias && !a.fs_out, "launch_gemm: a virtual operand reached a kernel that cannot form it (bcast_fold / footsum_fold and the kernel selection disagree)");
 	FIND_REQUIRE(!a.w_tr, "launch_gemm: an untransposed weight reached a kernel that cannot read it (gemm7_direct and the kernel selection disagree)");
@@ -559,26 +494,15 @@ static int launch_gemm(find_ctx* c, int amode, int epi, const GemmArgs& a, int64
 	return launch_gemm3(c, epi, b, feet, s);
 }
 
-// a K = 256, one-segment launch of this many rows per foot goes to gemm7 (launch_gemm's rule): its dX form may then read the model's weight
+// a K = 256, one-segment launch of this many rows per foot goes to gemm7 (launch_gemm's rule): its dX form then reads the model's weight
 // itself (Gemm2Args::w_tr) instead of a transposed copy
 static bool gemm7_direct(const find_ctx* c, int64_t V, int64_t feet) {
 	const int64_t units = cdiv(V, 32) * feet;
-#ifdef FIND_DIAG
-	if (!c->gemm7) return false;
-#endif
-	return c->direct_w && c->x3 && !(c->f16 && units >= c->gemm5_min_units) && units >= c->gemm6_min_units;
-}
-// ... whatever the weight's orientation: the launch will go to gemm7 (launch_gemm's rule)
-static bool gemm7_direct_units(const find_ctx* c, int64_t V, int64_t feet) {
-	const int64_t units = cdiv(V, 32) * feet;
-#ifdef FIND_DIAG
-	if (!c->gemm7) return false;
-#endif
 	return c->x3 && !(c->f16 && units >= c->gemm5_min_units) && units >= c->gemm6_min_units;
 }
 // a fused chain of this call will run on fused6_kernel (chain_prepare's rule): split_w_kernel reads every weight once anyway, in whatever
 // order the step asks for (FusedStep::wmode) -- no repack launch in front of the chain
-static bool chain_direct(const find_ctx* c) { return c->direct_w && c->x3 && c->fused6; }
+static bool chain_direct(const find_ctx* c) { return c->x3 && c->fused6; }
 
 // ---- fused chains (mlp_fused.h): one launch takes every 32-row tile through a list of layers
 struct Chain {
@@ -609,7 +533,6 @@ static int chain_prepare(find_ctx* c, Chain& ch, int64_t V, int64_t feet, hipStr
 	ch.a.V = (int)V;
 	ch.a.tiles_per_foot = (int)cdiv(V, 32 * ch.nt);
 	ch.a.ntiles = (int)(ch.a.tiles_per_foot * feet);
-	ch.a.ablate = c->ablate;
 	ch.x3 = false;
 	ch.prepared = true;
 	if (c->x3 && c->fused6 && w6 != nullptr) {
@@ -716,11 +639,7 @@ static bool use_fold(const find_ctx* c, bool a16, bool shared, int64_t n_feet, i
 	if (!c->bcast_fold || p->n_disp < 2 || p->n_col < 2) return false;
 	if (a16) return true;
 	const int64_t units = cdiv(V, 32) * n_feet;
-	bool x3_large = c->x3 && !c->f16 && shared && n_feet > 1 && units >= c->gemm6_min_units;
-#ifdef FIND_DIAG
-	x3_large = x3_large && c->gemm7;
-#endif
-	return x3_large;
+	return c->x3 && !c->f16 && shared && n_feet > 1 && units >= c->gemm6_min_units;
 }
 static void note_act16(find_ctx* c, const void* ws, bool a16, bool fold) {
 	for (auto& n : c->act16_notes) if (n.ws == ws) { n.a16 = a16; n.fold = fold; return; }
@@ -1078,7 +997,7 @@ static int weight_grad(find_ctx* c, Fork* fk, const float* dz, const float* x, i
 		return fk->stream(reduce_side);
 	};
 	float* pbuf = (db || S) ? b.pb : nullptr;
-	const int cus = (fk && fk->on) ? c->side_cus : c->num_cus;   // (the side streams may be confined to a part of the chip: cu_reserve)
+	const int cus = c->num_cus;
 	if (!pos) {
 		int nmain, spf;
 		if (c->f16) {
@@ -1107,7 +1026,7 @@ static int weight_grad(find_ctx* c, Fork* fk, const float* dz, const float* x, i
 			// Workgroups = slabs: one per CU when the launch has the chip to itself; HALF that inside a backward with side streams -- there it
 			// runs beside the dX GEMMs of the next layer, which take the other CUs anyway, and half the slabs are half the reduce's traffic
 			// (64 -> 32 MB per layer: headline step 1.76 -> 1.71 ms on one box; 96 and 64 workgroups are slower again)
-			const int wgs6 = c->dw6_wgs > 0 ? c->dw6_wgs : ((fk && fk->on) ? std::max(1, c->num_cus / 2) : c->num_cus);
+			const int wgs6 = (fk && fk->on) ? std::max(1, c->num_cus / 2) : c->num_cus;
 			const int want = (int)std::max<int64_t>(1, std::min<int64_t>(cpf16, cdiv(wgs6, feet)));
 			const int cps6 = (int)std::max<int64_t>(cdiv(cpf16, want), std::min<int>(c->dw2_min_cps, cpf16));
 			spf = (int)cdiv(cpf16, cps6);
@@ -1140,19 +1059,10 @@ static int weight_grad(find_ctx* c, Fork* fk, const float* dz, const float* x, i
 			nmain = (int)(feet * spf);
 			int lds = 0;
 			if (c->dw_lds_free == 0) FIND_TRY(prepare_kernel(c, K_DW2, &dw2_kernel, DW2_LDS, &lds));
-#ifdef FIND_DIAG
-			if (c->dw_lds_free == 3) FIND_TRY(prepare_kernel(c, K_DW2_REPRO, &dw2_repro_kernel, DW2_LDS, &lds));
-#endif
 			Dw2Args d2;
 			memset(&d2, 0, sizeof(d2));
 			d2.dz = dz; d2.dz_foot_stride = V * W; d2.x = x; d2.x_foot_stride = x_foot_stride;
 			d2.chunks_per_foot = cpf16; d2.tail_rows = (int)(V % 16); d2.spf = spf; d2.cps = cps2; d2.pw = b.pw; d2.pb = pbuf;
-			d2.dbg = FIND_DBG(c->dw2_verify);   // diagnosis: verify every published ring stage (tools/probe_lds_fault.py)
-#ifdef FIND_DIAG   // the reproducers of the co-residence fault
-			if (c->dw_lds_free == 3) hipLaunchKernelGGL(dw2_repro_kernel, dim3((unsigned)nmain), dim3(256), lds, s, d2);
-			else if (c->dw_lds_free == 2) hipLaunchKernelGGL(dw4_wide_kernel, dim3((unsigned)nmain), dim3(256), 0, s, d2);
-			else
-#endif
 			if (c->dw_lds_free == 1) hipLaunchKernelGGL(dw4_kernel, dim3((unsigned)nmain), dim3(512), 0, s, d2);
 			else hipLaunchKernelGGL(dw2_kernel, dim3((unsigned)nmain), dim3(256), lds, s, d2);
 			FIND_LAUNCH_CHECK("dw2_kernel");
@@ -1168,12 +1078,12 @@ static int weight_grad(find_ctx* c, Fork* fk, const float* dz, const float* x, i
 		return FIND_OK;
 	}
 	// Fourier layer: the inputs are regenerated from the positions.  dwpe_kernel (mlp_dwpe.h; pe >= 32): one k-tile of workgroups per 128
-	// frequencies, slabs of 2 pe + 32 columns; dw_kernel<AMODE_PE> (round 1, "dw_pe_lds_free" = 0): nkt k-tiles, slabs of 256 nkt columns.
-	// Either way the launch stays within one round of workgroups over the chip.
-	const bool lds_free = c->dw_pe_lds_free != 0 && p->pe_size >= 32;
+	// frequencies, slabs of 2 pe + 32 columns; dw_kernel<AMODE_PE> (round 1, LDS-staged; pe < 32): nkt k-tiles, slabs of 256 nkt columns.
+	// Either way the launch stays within one round of workgroups over the chip (at most 256).
+	const bool lds_free = p->pe_size >= 32;
 	const int nkt_launch = lds_free ? (int)cdiv(p->pe_size, 128) : nkt;
 	int spf, cps;
-	split_policy(feet, V, &spf, &cps, std::min<int64_t>(128, std::max<int64_t>(16, std::min(c->dw_pe_target, cus) / nkt_launch)));
+	split_policy(feet, V, &spf, &cps, std::min<int64_t>(128, std::max<int64_t>(16, std::min(256, cus) / nkt_launch)));
 	DwArgs a;
 	memset(&a, 0, sizeof(a));
 	a.dz = dz; a.dz_foot_stride = V * W;
@@ -1183,7 +1093,7 @@ static int weight_grad(find_ctx* c, Fork* fk, const float* dz, const float* x, i
 	a.pw = b.pw; a.pb = pbuf;
 	a.all_blocks = (c->ablate & 32) ? 1 : 0;
 	const int nsplit = (int)(feet * spf);
-	if (lds_free && (c->x3 || c->f16) && c->dwpe6) {   // bf16x3 calls (and the opt-in fp16 mode, whose Fourier layer keeps fp32-class arithmetic): the sin / cos columns on the bf16 matrix pipe, the x, y, z columns and the bias sums beside them
+	if (lds_free && (c->x3 || c->f16)) {   // bf16x3 calls (and the opt-in fp16 mode, whose Fourier layer keeps fp32-class arithmetic): the sin / cos columns on the bf16 matrix pipe, the x, y, z columns and the bias sums beside them
 		hipLaunchKernelGGL(dwpe6_kernel, dim3((unsigned)nkt_launch, (unsigned)nsplit), dim3(512), 0, s, a);
 		hipLaunchKernelGGL(dwxyz_kernel, dim3((unsigned)nsplit), dim3(1024), 0, s, a);
 	}
@@ -1218,18 +1128,17 @@ struct WgradGroup {
 // each at the fp32 peak) and writes a 256-KB slab that the grouped reduce reads back; one workgroup per CU (whole-LDS reservation), so the
 // launch runs in ceil(workgroups / CUs) rounds.  Few long splits leave CUs idle or pay a whole round for a few leftover workgroups; many
 // short ones pay the per-workgroup prologue + slab and make the reduce (~0.06 us per slab) the longer kernel: take the cheapest of
-// the candidates under this model ("group_spf" knob: 0 = model, n = force n splits per foot; measured with tools/fused_ab.py).
+// the candidates under this model.
 static void group_geometry(const find_ctx* c, int cpf16, int64_t feet, int jobs, int64_t max_slabs, int* spf_out, int* cps_out) {
 	auto take = [&](int s) { *cps_out = (int)cdiv(cpf16, s); *spf_out = (int)cdiv(cpf16, *cps_out); };
 	const int s_max = (int)std::max<int64_t>(1, std::min<int64_t>(cpf16, max_slabs / std::max<int64_t>(feet, 1)));
-	if (c->group_spf > 0) { take(std::min(c->group_spf, s_max)); return; }
 	double best = 1e30;
 	take(1);
 	for (int s = 1; s <= s_max; ++s) {
 		const int cps = (int)cdiv(cpf16, s);
 		if ((int)cdiv(cpf16, cps) != s || (cps < 2 && s > 1)) continue;   // (same geometry as a smaller s; single-chunk splits)
 		const int64_t wgs = feet * s * std::max(jobs, 1);
-		const double cost = (double)cdiv(wgs, c->side_cus) * (cps * 3.6 + 6.0) + wgs * 0.06;
+		const double cost = (double)cdiv(wgs, c->num_cus) * (cps * 3.6 + 6.0) + wgs * 0.06;
 		if (cost < best) { best = cost; take(s); }
 	}
 }
@@ -1238,7 +1147,7 @@ static int wgrad_group_add(find_ctx* c, WgradGroup& G, const BwdWs& b, const flo
 						   float* dw, int ld_out, float* db, float* S) {
 	FIND_REQUIRE(G.n < b.grp_jobs && G.n < DW2_MAX_JOBS && G.n < DW6_MAX_JOBS, "find_mlp_bwd: too many grouped weight gradients");
 	// bf16x3 calls: dw6_group_kernel (16-row chunks, rows past a foot's end zero-filled by the loads: ceil); the others dw4_group (tail rows folded)
-	G.x3 = c->x3 && c->dw6_group && c->dw_lds_free == 1;
+	G.x3 = c->x3 && c->dw_lds_free == 1;
 	const int cpf16 = G.x3 ? (int)cdiv(V, 16) : (int)(V / 16);
 	int spf = 1, cps2 = 1;
 	if (cpf16 > 0) group_geometry(c, cpf16, feet, G.live_jobs > 0 ? G.live_jobs : b.grp_jobs, b.grp_slabs, &spf, &cps2);
@@ -1267,7 +1176,7 @@ static int wgrad_group_launch(find_ctx* c, WgradGroup& G, hipStream_t s) {
 		int lds = 0;
 		FIND_TRY(prepare_kernel(c, K_DW6G, &dw6_group_kernel, DW6_LDS, &lds));
 		hipLaunchKernelGGL(dw6_group_kernel, dim3((unsigned)G.nmain, (unsigned)G.n), dim3(256), lds, s, G.d6);
-	} else if (c->dw_lds_free == 1 || c->dw_lds_free == 2) {
+	} else if (c->dw_lds_free == 1) {
 		hipLaunchKernelGGL(dw4_group_kernel, dim3((unsigned)G.nmain, (unsigned)G.n), dim3(512), 0, s, G.d);
 	} else {
 		int lds = 0;
@@ -1597,7 +1506,7 @@ static int mlp_bwd_body(find_ctx* c, Fork& fk, const find_mlp_params* p, const D
 	// foot-summed dZ, which used to be a 50-70-us fp32-MFMA launch of its own per head -- travel in ONE grouped launch behind the trunk's dX chain.
 	WgradGroup G;
 	const bool grouped_v = fused && d.shared && !c->f16 && b.grp_pw != nullptr;
-	G.live_jobs = (p->n_trunk - 1) + (c->group_head0 ? (act_d ? 1 : 0) + (act_c ? 1 : 0) : 0);
+	G.live_jobs = (p->n_trunk - 1) + (act_d ? 1 : 0) + (act_c ? 1 : 0);
 	auto head_bwd = [&](int nl, float* const* act, float* const* dzbuf, int& cur, bool colour, float* const* gw, float* const* gb,
 						const float* w0full, int ld0, const float* lat, int L, float* S, float* glat, float* zs, float* ps, int side) -> int {
 		int fsum_pairs = 0;
@@ -1623,7 +1532,7 @@ static int mlp_bwd_body(find_ctx* c, Fork& fk, const find_mlp_params* p, const D
 			}
 			const WT t = colour ? wt_C(l) : wt_D(l);
 			// footsum_fold: this dX GEMM's output is the broadcast layer's dZ, of which only sums are read (below): formed inside the GEMM
-			fsum_pairs = (l == 1 && v.P && !a16 && c->footsum_fold && zs != nullptr && gemm7_direct_units(c, V, n_feet)) ? gemm7_fsum_pairs(c, V, n_feet) : 0;
+			fsum_pairs = (l == 1 && v.P && !a16 && c->footsum_fold && zs != nullptr && gemm7_direct(c, V, n_feet)) ? gemm7_fsum_pairs(c, V, n_feet) : 0;
 			if (fsum_pairs > 0) {
 				float* const fs1 = colour ? b.fs1C : b.fs1D;
 				FIND_TRY(linear_bwd_dx(c, dzbuf[cur], t.w, t.ld, t.tr, xin, dzbuf[cur + 1], V, n_feet, s, a16, v.bias, v.bstride, zs, fs1 - zs, ps));
@@ -1646,7 +1555,7 @@ static int mlp_bwd_body(find_ctx* c, Fork& fk, const find_mlp_params* p, const D
 			FIND_LAUNCH_CHECK("footsum (folded)");
 			BwdWs bk = b;
 			bk.pw = b.pw_t[side]; bk.pb = b.pb_t[side];
-			if (grouped_v && c->group_head0) FIND_TRY(wgrad_group_add(c, G, b, zs, hl, 0, 1, V, gw[0], ld0, nullptr, nullptr));
+			if (grouped_v) FIND_TRY(wgrad_group_add(c, G, b, zs, hl, 0, 1, V, gw[0], ld0, nullptr, nullptr));
 			else FIND_TRY(weight_grad(c, &fk, zs, hl, 0, nullptr, 0, p, 1, 1, V, bk, gw[0], ld0, W, 0, nullptr, nullptr, q0));
 		} else if (d.shared) {
 			// every foot multiplies the same trunk rows: reduce dZ0 over feet first (one pass), then M = V GEMMs
@@ -1665,7 +1574,7 @@ static int mlp_bwd_body(find_ctx* c, Fork& fk, const find_mlp_params* p, const D
 			if (L > 0) db_late = gb[0];
 			else hipLaunchKernelGGL(colsum_small_kernel, dim3(1), dim3(256), 0, q0, S, (int)n_feet, gb[0]);
 			FIND_LAUNCH_CHECK("footsum");
-			if (grouped_v && c->group_head0) FIND_TRY(wgrad_group_add(c, G, b, zs, hl, 0, 1, V, gw[0], ld0, nullptr, nullptr));
+			if (grouped_v) FIND_TRY(wgrad_group_add(c, G, b, zs, hl, 0, 1, V, gw[0], ld0, nullptr, nullptr));
 			else FIND_TRY(weight_grad(c, &fk, zs, hl, 0, nullptr, 0, p, 1, 1, V, bk, gw[0], ld0, W, 0, nullptr, nullptr, q0));
 		} else {
 			fk.fork_to(Q);
@@ -1739,7 +1648,7 @@ static int mlp_bwd_body(find_ctx* c, Fork& fk, const find_mlp_params* p, const D
 			ct += 1;
 		}
 	}
-	if (fused && d.shared && fk.on && c->pe_on_t2) {
+	if (fused && d.shared && fk.on) {
 		// (round 6: on Q the Fourier layer's weight gradient queued behind the last large layer's dw6 AND its slab reduce -- 60 us after the
 		// trunk's dX chain had produced its input, at the very end of the step; T2 is idle by then, and its slab set is the Fourier layer's size)
 		fk.fork_to(T2);
@@ -1951,35 +1860,15 @@ extern "C" int find_ctx_stream_beside(find_ctx* c, void* caller_stream, void* co
 // chooses its side streams among a dozen candidates by probing (once per context, ~20 ms).
 namespace find {
 namespace mlp {
-// a side-stream candidate: non-blocking, or -- cu_reserve -- confined to the CUs the mask leaves (bit i of the mask = CU i / 8 of XCD i % 8,
-// the driver's order on multi-XCD parts: clearing the low 8 R bits takes R CUs from every XCD)
-static hipError_t create_side_stream(find_ctx* c, hipStream_t* out) {
-	if (c->cu_reserve <= 0) return hipStreamCreateWithFlags(out, hipStreamNonBlocking);
-	uint32_t mask[16] = {};
-	const int ncu = std::min(c->num_cus, 512), lo = std::min(8 * c->cu_reserve, ncu - 8);
-	for (int i = lo; i < ncu; ++i) mask[i >> 5] |= 1u << (i & 31);
-	return hipExtStreamCreateWithCUMask(out, (uint32_t)((ncu + 31) / 32), mask);
-}
-
 static int bind_side_streams(find_ctx* c, hipStream_t caller) {
 	c->side_bound = true;   // (one attempt: a failure below keeps the streams as created)
 	constexpr int N_CAND = 12;
 	hipStream_t st[1 + N_CAND];
 	st[0] = caller;
 	int n = 1;
-	if (c->cu_reserve > 0) {
-		// the streams find_ctx_create made carry no mask: replace them
-		for (int k = 0; k < N_SIDE; ++k) {
-			hipStream_t m = nullptr;
-			if (create_side_stream(c, &m) != hipSuccess) { set_error("find_ctx: hipExtStreamCreateWithCUMask failed"); return FIND_ELAUNCH; }
-			(void)hipStreamDestroy(c->side[k]);
-			c->side[k] = m;
-		}
-		c->side_cus = c->num_cus - std::min(8 * c->cu_reserve, c->num_cus - 8);
-	}
 	for (int k = 0; k < N_SIDE; ++k) st[n++] = c->side[k];
 	for (; n < 1 + N_CAND; ++n)
-		if (create_side_stream(c, &st[n]) != hipSuccess) break;
+		if (hipStreamCreateWithFlags(&st[n], hipStreamNonBlocking) != hipSuccess) break;
 	int g[1 + N_CAND];
 	int rc = stream_groups(st, n, c->ev[0], c->ev[1], g);
 	int pick[N_SIDE] = {-1, -1, -1, -1};
@@ -1992,9 +1881,8 @@ static int bind_side_streams(find_ctx* c, hipStream_t caller) {
 				if (fresh) { pick[k] = i; ++ng; }
 			}
 		if (ng == 3) {
-			const int rq = pick[c->r_queue];
-			for (int i = 1; i < n && pick[3] < 0; ++i)   // R: another stream on T2's queue (knob r_queue: Q's or T1's)
-				if (i != pick[0] && i != pick[1] && i != pick[2] && g[i] == g[rq]) pick[3] = i;
+			for (int i = 1; i < n && pick[3] < 0; ++i)   // R: another stream on T2's queue
+				if (i != pick[0] && i != pick[1] && i != pick[2] && g[i] == g[pick[2]]) pick[3] = i;
 			if (pick[3] < 0)   // (none: any stream that is not on the caller's queue and not a pick)
 				for (int i = 1; i < n && pick[3] < 0; ++i)
 					if (g[i] != 0 && i != pick[0] && i != pick[1] && i != pick[2]) pick[3] = i;
@@ -2037,7 +1925,6 @@ extern "C" int find_ctx_create(int device, find_ctx** out) {
 	int v = 0;
 	if ((e = hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, device)) != hipSuccess) return fail("CU count", e);
 	c->num_cus = v > 0 ? v : 256;
-	c->side_cus = c->num_cus;
 	if ((e = hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, device)) != hipSuccess) return fail("LDS size", e);
 	c->lds_bytes = v;
 	for (int i = 0; i < N_SIDE; ++i)
@@ -2066,31 +1953,32 @@ extern "C" int find_ctx_destroy(find_ctx* c) {
 namespace {
 struct Knob { const char* key; int find_ctx::*field; int64_t lo, hi; };
 const Knob KNOBS[] = {
-#ifdef FIND_DIAG
-	{"gemm7", &find_ctx::gemm7, 0, 1}, {"x3_abl", &find_ctx::x3_abl, 0, 15},
-#endif
 	{"gemm4_small", &find_ctx::gemm4_small, 0, INT32_MAX},
-	{"dw_pe_target", &find_ctx::dw_pe_target, 16, INT32_MAX}, {"dw_pe_lds_free", &find_ctx::dw_pe_lds_free, 0, 1}, {"dw2_min_cps", &find_ctx::dw2_min_cps, 1, INT32_MAX},
-	{"bwd_streams", &find_ctx::bwd_streams, 0, 1}, {"fwd_streams", &find_ctx::fwd_streams, 0, 1}, {"reduce_stream", &find_ctx::reduce_stream, 0, 1},
-	{"gemm5_min_units", &find_ctx::gemm5_min_units, 0, INT32_MAX}, {"fused_max_units", &find_ctx::fused_max_units, 0, 1024}, {"fused6", &find_ctx::fused6, 0, 1}, {"dw6_wgs", &find_ctx::dw6_wgs, 0, 512}, {"bind_streams", &find_ctx::bind_streams, 0, 1}, {"direct_w", &find_ctx::direct_w, 0, 1}, {"dw6_group", &find_ctx::dw6_group, 0, 1}, {"dwpe6", &find_ctx::dwpe6, 0, 1}, {"r_queue", &find_ctx::r_queue, 0, 2}, {"cu_reserve", &find_ctx::cu_reserve, 0, 16}, {"group_spf", &find_ctx::group_spf, 0, 4096}, {"dw_lds_free", &find_ctx::dw_lds_free, 0, FIND_DIAG_ON ? 3 : 1}, {"reduce_exclusive", &find_ctx::reduce_exclusive, 0, 2}, {"mlp_f16", &find_ctx::mlp_f16, 0, 2}, {"gemm6_min_units", &find_ctx::gemm6_min_units, 0, INT32_MAX}, {"lds_exclusive", &find_ctx::lds_exclusive, 0, 1}, {"defer_join", &find_ctx::defer_join, 0, 1}, {"act16", &find_ctx::act16, 0, 1}, {"bcast_fold", &find_ctx::bcast_fold, 0, 1}, {"group_head0", &find_ctx::group_head0, 0, 1}, {"footsum_fold", &find_ctx::footsum_fold, 0, 1}, {"pe_on_t2", &find_ctx::pe_on_t2, 0, 1},
+	{"gemm5_min_units", &find_ctx::gemm5_min_units, 0, INT32_MAX},
+	{"gemm6_min_units", &find_ctx::gemm6_min_units, 0, INT32_MAX},
+	{"mlp_f16", &find_ctx::mlp_f16, 0, 2},
+	{"fused_max_units", &find_ctx::fused_max_units, 0, 1024},
+	{"fused6", &find_ctx::fused6, 0, 1},
+	{"dw2_min_cps", &find_ctx::dw2_min_cps, 1, INT32_MAX},
+	{"dw_lds_free", &find_ctx::dw_lds_free, 0, 1},
+	{"lds_exclusive", &find_ctx::lds_exclusive, 0, 1},
+	{"reduce_exclusive", &find_ctx::reduce_exclusive, 0, 2},
+	{"bwd_streams", &find_ctx::bwd_streams, 0, 1},
+	{"fwd_streams", &find_ctx::fwd_streams, 0, 1},
+	{"reduce_stream", &find_ctx::reduce_stream, 0, 1},
+	{"bind_streams", &find_ctx::bind_streams, 0, 1},
+	{"defer_join", &find_ctx::defer_join, 0, 1},
+	{"act16", &find_ctx::act16, 0, 1},
+	{"bcast_fold", &find_ctx::bcast_fold, 0, 1},
+	{"footsum_fold", &find_ctx::footsum_fold, 0, 1},
 };
 }  // namespace
 
 extern "C" int find_ctx_set(find_ctx* c, const char* key, int64_t value) {
 	FIND_REQUIRE(c != nullptr && key != nullptr, "find_ctx_set: NULL argument");
-#ifdef FIND_DIAG
-	if (strcmp(key, "dbg") == 0) {  // device pointer to >= 4 * grid uint64 (profiling only)
-		c->dbg = reinterpret_cast<unsigned long long*>(value);
-		return FIND_OK;
-	}
-	if (strcmp(key, "dw2_verify") == 0) {  // device pointer to 8 + 64 * 8 uint64 (diagnosis only)
-		c->dw2_verify = reinterpret_cast<unsigned long long*>(value);
-		return FIND_OK;
-	}
-#endif
 	if (strcmp(key, "ablate") == 0) {
-		FIND_REQUIRE(value >= 0 && value <= INT32_MAX && (FIND_DIAG_ON || (value & ~(int64_t)find::MLP_SWITCHES) == 0),
-		             "find_ctx_set: ablate = %lld has bits outside the result-preserving switches 0x%x (the others exist in libfind_hip_diag.so only)", (long long)value, find::MLP_SWITCHES);
+		FIND_REQUIRE(value >= 0 && value <= INT32_MAX && (value & ~(int64_t)find::MLP_SWITCHES) == 0,
+		             "find_ctx_set: ablate = %lld has bits outside the result-preserving switches 0x%x", (long long)value, find::MLP_SWITCHES);
 		c->ablate = (int)value;
 		return FIND_OK;
 	}
@@ -2112,14 +2000,12 @@ extern "C" int find_ctx_set(find_ctx* c, const char* key, int64_t value) {
 extern "C" int find_ctx_get(const find_ctx* c, const char* key, int64_t* value) {
 	FIND_REQUIRE(c != nullptr && key != nullptr && value != nullptr, "find_ctx_get: NULL argument");
 	if (strcmp(key, "num_cus") == 0) { *value = c->num_cus; return FIND_OK; }
-	if (strcmp(key, "side_cus") == 0) { *value = c->side_cus; return FIND_OK; }
 	if (strcmp(key, "pending") == 0) { *value = (c->pend[0] || c->pend[1] || c->pend[2] || c->pend[3]) ? 1 : 0; return FIND_OK; }
 	if (strcmp(key, "lds_bytes") == 0) { *value = c->lds_bytes; return FIND_OK; }
 	if (strcmp(key, "device") == 0) { *value = c->device; return FIND_OK; }
 	if (strcmp(key, "events_per_call_max") == 0) { *value = c->events_per_call_max; return FIND_OK; }
 	if (strcmp(key, "gemm4_min_units") == 0) { *value = c->gemm4_min_units; return FIND_OK; }
 	if (strcmp(key, "ablate") == 0) { *value = c->ablate; return FIND_OK; }
-	if (strcmp(key, "diag") == 0) { *value = FIND_DIAG_ON; return FIND_OK; }
 	for (const Knob& k : KNOBS)
 		if (strcmp(key, k.key) == 0) { *value = c->*(k.field); return FIND_OK; }
 	set_error("find_ctx_get: unknown key %s", key);
@@ -2131,10 +2017,3 @@ extern "C" int find_render_switches(int64_t bits) {
 	find::g_raster_ablate = (int)bits;
 	return FIND_OK;
 }
-
-#ifdef FIND_DIAG
-extern "C" int find_debug_raster_ablate(int64_t bits) {   // every bit, also those under which the render is wrong (include/find_hip_diag.h)
-	find::g_raster_ablate = (int)bits;
-	return FIND_OK;
-}
-#endif

@@ -8,8 +8,7 @@
 // ROUND 2: this kernel was the victim of the co-residence fault (mlp.hip): 312 registers per lane, and a wave above 256 registers gets
 // wrong register contents when waves of another kernel share its SIMD.  dw2_kernel now claims the whole register file (nothing fits
 // beside it: 0 wrong tensors in 600 stress passes) and is selectable with "dw_lds_free" = 0; the default is dw4_kernel (mlp_dw4.h: no
-// LDS, <= 256 registers, 148 against 139-142 us per 110 240-row weight gradient including the slab reduce, the same step time);
-// dw2_repro_kernel is the kernel as round 1 had it, the reproducer.
+// LDS, <= 256 registers, 148 against 139-142 us per 110 240-row weight gradient including the slab reduce, the same step time).
 //
 //   * chunk = 16 rows of dZ (16 KB) + 16 rows of X (16 KB), each row one 1-KB global_load_lds_dwordx4; 3-stage ring;
 //   * MFMA operands come from LDS with ONE ds_read_b128 per operand per k-pair: lane l reads columns 4(l&31)..+3 of row
@@ -35,55 +34,11 @@ struct Dw2Args {
 	int cps;                 // chunks per split
 	float* pw;               // [n_feet*spf][256][256]
 	float* pb;               // [n_feet*spf][256] or nullptr
-	unsigned long long* dbg; // diagnosis only (tools/probe_lds_fault.py): every published ring stage is compared with its source in HBM
+	void* pad;               // unused: keeps a job of Dw2Group at 64 bytes (the group kernels index the array with a shift)
 };
 
 constexpr int DW2_STAGE = 2 * 16 * 1024;                // dZ rows then X rows
 constexpr int DW2_LDS = 3 * DW2_STAGE + 4 * 256 * 4;    // + bias reduction scratch
-
-#ifdef FIND_DIAG
-// Diagnosis of the LDS co-residence fault (mlp.hip): thread t compares bytes [128 t, 128 t + 128) of a published stage (16 dZ rows then 16 X
-// rows of 1 KB) with the same bytes read straight from HBM.  Log layout (uint64): [0] mismatching 16-byte pieces, [1] stages checked by
-// thread 0, [2] stages checked by workgroups whose LDS base is not 0, then up to 64 records of 8 words:
-// {split | chunk << 32, stage | tid << 8 | piece << 24, HW_REG_LDS_ALLOC, HW_REG_HW_ID, got.x bits | expected.x bits << 32,
-//  1 if the piece equals what the stage held three chunks ago (stale) else 0, XCC id, 0}.
-__device__ __noinline__ void dw2_verify_stage(unsigned long long* log, const char* stage, const float* zsrc, const float* xsrc, const float* zold,
-											   const float* xold, int split, int chunk, int stage_idx) {
-	const int tid = threadIdx.x;
-	const int row = tid >> 3, part = tid & 7;   // 32 rows x 8 pieces of 128 B
-	const float* src = row < 16 ? zsrc + row * 256 + part * 32 : xsrc + (row - 16) * 256 + part * 32;
-	const float* old = row < 16 ? (zold ? zold + row * 256 + part * 32 : nullptr) : (xold ? xold + (row - 16) * 256 + part * 32 : nullptr);
-	const unsigned alloc = __builtin_amdgcn_s_getreg((31 << 11) | 6);
-	if (tid == 0) {
-		atomicAdd(log + 1, 1ull);
-		if (alloc & 0xFF) atomicAdd(log + 2, 1ull);
-	}
-#pragma unroll 1
-	for (int i = 0; i < 8; ++i) {
-		const float4 got = *reinterpret_cast<const float4*>(stage + row * 1024 + part * 128 + i * 16);
-		const float4 want = *reinterpret_cast<const float4*>(src + i * 4);
-		if (got.x != want.x || got.y != want.y || got.z != want.z || got.w != want.w) {
-			const unsigned long long n = atomicAdd(log, 1ull);
-			if (n < 64) {
-				unsigned long long* r = log + 8 + n * 8;
-				int stale = 0;
-				if (old) {
-					const float4 o = *reinterpret_cast<const float4*>(old + i * 4);
-					stale = (got.x == o.x && got.y == o.y && got.z == o.z && got.w == o.w) ? 1 : 0;
-				}
-				r[0] = (unsigned)split | ((unsigned long long)chunk << 32);
-				r[1] = (unsigned)stage_idx | ((unsigned)tid << 8) | ((unsigned)i << 24);
-				r[2] = alloc;
-				r[3] = __builtin_amdgcn_s_getreg((31 << 11) | 4);
-				r[4] = __float_as_uint(got.x) | ((unsigned long long)__float_as_uint(want.x) << 32);
-				r[5] = stale;
-				r[6] = __builtin_amdgcn_s_getreg((31 << 11) | 20);
-				r[7] = 0;
-			}
-		}
-	}
-}
-#endif
 
 __device__ __forceinline__ void dw2_body(const Dw2Args& g, const int split) {
 	extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -186,19 +141,11 @@ __device__ __forceinline__ void dw2_body(const Dw2Args& g, const int split) {
 			const char* nsb = smem + ns * DW2_STAGE;
 			const int ahead = issued - (consumed + 2);
 			mfma_step(a0, b0);
-			// (diagnosis) the stage this wave has just consumed must still hold chunk c: stage index + 8 in the log
-#ifdef FIND_DIAG
-			if (g.dbg) dw2_verify_stage(g.dbg, sb, zb + (int64_t)c * 4096, xb + (int64_t)c * 4096, nullptr, nullptr, split, c, cs + 8);
-#endif
 			if (more) {
 				asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 				if (ahead <= 0) FIND_WAIT_VMCNT(0);
 				else FIND_WAIT_VMCNT(8);
 				__builtin_amdgcn_s_barrier();
-#ifdef FIND_DIAG
-				if (g.dbg) dw2_verify_stage(g.dbg, nsb, zb + (int64_t)(c + 1) * 4096, xb + (int64_t)(c + 1) * 4096, c >= 2 ? zb + (int64_t)(c - 2) * 4096 : nullptr,
-											c >= 2 ? xb + (int64_t)(c - 2) * 4096 : nullptr, split, c + 1, ns);
-#endif
 			}
 			__builtin_amdgcn_sched_barrier(0);
 			mfma_ja(a1, b1, 0);
@@ -274,10 +221,6 @@ __global__ __launch_bounds__(256, 1) void dw2_kernel(const Dw2Args g) {
 	FIND_CLAIM_WHOLE_REGISTER_FILE();   // 312 registers by itself: the fault's victim (see the macro); with all 512, 0 wrong tensors in 450 stress passes
 	dw2_body(g, blockIdx.x);
 }
-#ifdef FIND_DIAG
-// The kernel as round 1 had it (312 registers, foreign waves fit beside it): the reproducer of the fault ("dw_lds_free" = 3), nothing else.
-__global__ __launch_bounds__(256, 1) void dw2_repro_kernel(const Dw2Args g) { dw2_body(g, blockIdx.x); }
-#endif
 
 // Several weight gradients of the same geometry in ONE launch (blockIdx.y = job): the small calls -- batch 1, the texture samples --
 // have eleven 256 x 256 weight gradients of 54 workgroups each; launched one by one they neither fill the chip nor overlap well.
@@ -288,7 +231,7 @@ __global__ __launch_bounds__(256, 1) void dw2_group_kernel(const Dw2Group grp) {
 	Dw2Args g;   // (fields copied one by one: a reference into the kernel-argument array makes the compiler copy the array to scratch)
 	g.dz = grp.job[j].dz; g.dz_foot_stride = grp.job[j].dz_foot_stride; g.x = grp.job[j].x; g.x_foot_stride = grp.job[j].x_foot_stride;
 	g.chunks_per_foot = grp.job[j].chunks_per_foot; g.tail_rows = grp.job[j].tail_rows; g.spf = grp.job[j].spf; g.cps = grp.job[j].cps;
-	g.pw = grp.job[j].pw; g.pb = grp.job[j].pb; g.dbg = nullptr;
+	g.pw = grp.job[j].pw; g.pb = grp.job[j].pb;
 	FIND_CLAIM_WHOLE_REGISTER_FILE();
 	dw2_body(g, blockIdx.x);
 }

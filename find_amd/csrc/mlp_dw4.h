@@ -16,13 +16,13 @@ namespace mlp {
 
 constexpr int DW4_PD = 6;   // prefetch distance in k-pairs (ring of 8)
 
-template <int NB>   // 32-column blocks of k per wave: 2 (eight waves, the product) or 4 (four waves with dw2's 128 x 128 tiles: diagnosis)
 __device__ __forceinline__ void dw4_body(const Dw2Args& g, const int split) {
+	constexpr int NB = 2;   // 32-column blocks of k per wave
 	typedef float bvec __attribute__((ext_vector_type(NB)));
 	const int tid = threadIdx.x;
 	const int lane = tid & 63;
 	const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-	const int wn = NB == 2 ? wave >> 2 : wave >> 1, wk = NB == 2 ? wave & 3 : wave & 1;
+	const int wn = wave >> 2, wk = wave & 3;
 	const int li = lane & 31, fh = lane >> 5;
 	const int foot = split / g.spf;
 	const int sidx = split - foot * g.spf;
@@ -118,19 +118,11 @@ __device__ __forceinline__ void dw4_body(const Dw2Args& g, const int split) {
 			for (int r = 0; r < 16; ++r) {
 				const int nrow = 4 * ((r & 3) + 8 * (r >> 2)) + ja;
 				// (value copies: __builtin_bit_cast on a vector-element lvalue reads element 0)
-				if constexpr (NB == 2) {
-					typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-					u32x2 v;
-					const float f0 = acc[ja][0][r], f1 = acc[ja][1][r];
-					v.x = __float_as_uint(f0); v.y = __float_as_uint(f1);
-					__builtin_amdgcn_raw_buffer_store_b64(v, rsrc, voff, nrow * 1024, 0);
-				} else {
-					typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-					u32x4 v;
-					const float f0 = acc[ja][0][r], f1 = acc[ja][1][r], f2 = acc[ja][2 % NB][r], f3 = acc[ja][3 % NB][r];
-					v.x = __float_as_uint(f0); v.y = __float_as_uint(f1); v.z = __float_as_uint(f2); v.w = __float_as_uint(f3);
-					store_b128(v, rsrc, voff, nrow * 1024);
-				}
+				typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+				u32x2 v;
+				const float f0 = acc[ja][0][r], f1 = acc[ja][1][r];
+				v.x = __float_as_uint(f0); v.y = __float_as_uint(f1);
+				__builtin_amdgcn_raw_buffer_store_b64(v, rsrc, voff, nrow * 1024, 0);
 			}
 	}
 	if (do_bias) {
@@ -142,12 +134,7 @@ __device__ __forceinline__ void dw4_body(const Dw2Args& g, const int split) {
 	}
 }
 
-__global__ __launch_bounds__(512) void dw4_kernel(const Dw2Args g) { dw4_body<2>(g, blockIdx.x); }
-#ifdef FIND_DIAG
-// (diagnosis, "dw_lds_free" = 2: dw2's register shape without its LDS ring -- four waves, one per SIMD, 128 x 128 tiles, 328 registers with 256
-// accumulators in AGPRs.  It shows the fault of dw2 without any LDS in the kernel: what matters is a wave above 256 registers, mlp_kernels.h)
-__global__ __launch_bounds__(256, 1) void dw4_wide_kernel(const Dw2Args g) { dw4_body<4>(g, blockIdx.x); }
-#endif
+__global__ __launch_bounds__(512) void dw4_kernel(const Dw2Args g) { dw4_body(g, blockIdx.x); }
 
 // Several weight gradients of the same geometry in ONE launch (blockIdx.y = job), as dw2_group_kernel.
 __global__ __launch_bounds__(512) void dw4_group_kernel(const Dw2Group grp) {
@@ -155,8 +142,8 @@ __global__ __launch_bounds__(512) void dw4_group_kernel(const Dw2Group grp) {
 	Dw2Args g;   // (fields copied one by one: a reference into the kernel-argument array makes the compiler copy the array to scratch)
 	g.dz = grp.job[j].dz; g.dz_foot_stride = grp.job[j].dz_foot_stride; g.x = grp.job[j].x; g.x_foot_stride = grp.job[j].x_foot_stride;
 	g.chunks_per_foot = grp.job[j].chunks_per_foot; g.tail_rows = grp.job[j].tail_rows; g.spf = grp.job[j].spf; g.cps = grp.job[j].cps;
-	g.pw = grp.job[j].pw; g.pb = grp.job[j].pb; g.dbg = nullptr;
-	dw4_body<2>(g, blockIdx.x);
+	g.pw = grp.job[j].pw; g.pb = grp.job[j].pb;
+	dw4_body(g, blockIdx.x);
 }
 
 }  // namespace mlp

@@ -68,7 +68,6 @@ struct FusedArgs {
 	int V;                    // rows per foot
 	int tiles_per_foot;
 	int ntiles;
-	int ablate;               // profiling only: 1 no W staging (loads + LDS stores), 2 no MFMAs, 4 no epilogue, 8 no Fourier features
 	const void* w6;           // fused6_kernel (mlp_fused6.h): the chain's weights as fragment-ordered bf16 planes, [8 waves][total_steps][3][64] x 16 B
 	int total_steps;          //   16-k steps of all GEMM steps of the chain
 };
@@ -207,7 +206,7 @@ __global__ __launch_bounds__(512, 2) void fused_chain_kernel(const FusedArgs g) 
 			const float* const wfrag1 = Wc1 + li * FW_LD + lh * 4;
 #define FUSED_CHUNK(PAR, c_)                                                                                                   \
 			do {                                                                                                               \
-				if (!FIND_ABL(g.ablate, 1)) { if (PAR) FUSED_W_LOAD(wb, pf_w, pf_ldw, pf_c); else FUSED_W_LOAD(wa, pf_w, pf_ldw, pf_c); }   \
+				if (PAR) FUSED_W_LOAD(wb, pf_w, pf_ldw, pf_c); else FUSED_W_LOAD(wa, pf_w, pf_ldw, pf_c);                      \
 				pf_advance();                                                                                                  \
 				__builtin_amdgcn_sched_barrier(0); /* the prefetch is issued BEFORE the MFMAs (else it sinks next to its store) */ \
 				const float* xa = xa0 + (s.src_kind == FS_SRC_PE ? ((c_) & 7) : (c_)) * 32;                                    \
@@ -224,23 +223,21 @@ __global__ __launch_bounds__(512, 2) void fused_chain_kernel(const FusedArgs g) 
 					}                                                                                                          \
 					__builtin_amdgcn_sched_barrier(0);                                                                         \
 					const float4 b = fb[cur];                                                                                  \
-					if (!FIND_ABL(g.ablate, 2)) {                                                                                     \
-						_Pragma("unroll") for (int rt = 0; rt < NT; ++rt) {                                                    \
-							const float4 a = fa[cur][rt];                                                                      \
-							acc[rt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, acc[rt], 0, 0, 0);                        \
-							acc[rt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.y, acc[rt], 0, 0, 0);                        \
-							acc[rt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b.z, acc[rt], 0, 0, 0);                        \
-							acc[rt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b.w, acc[rt], 0, 0, 0);                        \
-						}                                                                                                      \
-					} else { acc[0][0] += fa[cur][0].x + b.x; }                                                                \
+					_Pragma("unroll") for (int rt = 0; rt < NT; ++rt) {                                                        \
+						const float4 a = fa[cur][rt];                                                                          \
+						acc[rt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, acc[rt], 0, 0, 0);                            \
+						acc[rt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.y, acc[rt], 0, 0, 0);                            \
+						acc[rt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b.z, acc[rt], 0, 0, 0);                            \
+						acc[rt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b.w, acc[rt], 0, 0, 0);                            \
+					}                                                                                                          \
 					__builtin_amdgcn_sched_barrier(0);                                                                         \
 				}                                                                                                              \
 				/* chunk k + 1 (requested one iteration ago) moves into the stage chunk k - 1 has left; the ring is private to */ \
 				/* the wave, whose LDS operations complete in order: no barrier */                                              \
-				if (!FIND_ABL(g.ablate, 1)) { if (PAR) FUSED_W_STORE(wa, Wc0); else FUSED_W_STORE(wb, Wc1); }                          \
+				if (PAR) FUSED_W_STORE(wa, Wc0); else FUSED_W_STORE(wb, Wc1);                                                  \
 			} while (0)
 			for (int c = 0; c < nchunk; c += 2) {
-				if (s.src_kind == FS_SRC_PE && (c & 7) == 0 && !FIND_ABL(g.ablate, 8)) {
+				if (s.src_kind == FS_SRC_PE && (c & 7) == 0) {
 					// regenerate the X tile with the Fourier features of k-tile c / 8; a thread fills 16 columns of one row
 					if (c > 0) __syncthreads();   // the previous k-tile has been consumed by every wave
 					const int seg = tid & 15;
@@ -272,7 +269,7 @@ __global__ __launch_bounds__(512, 2) void fused_chain_kernel(const FusedArgs g) 
 				FUSED_CHUNK(1, c + 1);
 			}
 #undef FUSED_CHUNK
-			if (s.keep || FIND_ABL(g.ablate, 4)) continue;
+			if (s.keep) continue;
 
 			// ---- epilogue: bias + ReLU / mask, store to HBM, hand the tile to the next step through LDS
 			__syncthreads();   // every wave has multiplied its last chunk: nobody reads X any more

@@ -56,8 +56,7 @@ struct Gemm2Args {
 	float* fs_out;          // gemm7<.., FSUM>: [2][V][ldy] sums over the feet (slot 0 + slot 1 = the sum: mlp_gemm7.h)
 	int64_t fs_slot_stride; // floats between the two slots
 	float* cs_out;          // gemm7<.., FSUM>: [workgroup pair][foot][256] per-foot column sums
-	int ablate;             // profiling only: bit0 skip DMA issue, bit1 skip epilogue stores, bit2 skip MFMAs
-	unsigned long long* dbg; // profiling only: per-workgroup [total, wait+barrier, epilogue, lgkm-wait] shader cycles (wave 0)
+	int ablate;             // the context's switches (MLP_SWITCHES); read by gemm4: bit 16 = no s_setprio
 };
 
 #define FIND_WAIT_VMCNT(N) asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory")

@@ -97,8 +97,6 @@ __global__ __launch_bounds__(256, FIND_GEMM3_MIN_WGS) void gemm3_kernel(const Ge
 	const int64_t a_foot_stride = g.a_foot_stride;
 	const int lda = g.lda, ldw = g.ldw, ldy = g.ldy, V = g.V, nchunk = g.nchunk, tpf = g.tiles_per_foot;
 	const int NC = g.nseg * g.nchunk;
-	const int ablate = FIND_DIAG_ON ? g.ablate : 0;   // (bits 1, 2: diagnostics build only)
-	unsigned long long* const dbg = FIND_DBG(g.dbg);
 
 	const int tid = threadIdx.x;
 	const int lane = tid & 63;
@@ -190,7 +188,7 @@ __global__ __launch_bounds__(256, FIND_GEMM3_MIN_WGS) void gemm3_kernel(const Ge
 	};
 
 	// ---- prologue: fill the ring, publish chunk 0, read its first fragments
-	for (int k = 0; k < 3 && pt < t1 && !(ablate & 1); ++k) { issue_prepare(); issue_w0(); issue_w1(); issue_a(); issue_advance(); }
+	for (int k = 0; k < 3 && pt < t1; ++k) { issue_prepare(); issue_w0(); issue_w1(); issue_a(); issue_advance(); }
 	if (issued >= 3) {
 		if constexpr (ND == 10) FIND_WAIT_VMCNT(20); else FIND_WAIT_VMCNT(24);
 	} else if (issued == 2) {
@@ -211,8 +209,6 @@ __global__ __launch_bounds__(256, FIND_GEMM3_MIN_WGS) void gemm3_kernel(const Ge
 
 	int cs = 0;  // ring stage of the chunk being multiplied
 	int since_epi = 99;
-	unsigned long long c_wait = 0, c_epi = 0, c_lgkm = 0;
-	const unsigned long long c_start = dbg ? __builtin_amdgcn_s_memtime() : 0;
 
 	int foot = t0 / tpf;
 	int tif = t0 - foot * tpf;
@@ -272,7 +268,7 @@ __global__ __launch_bounds__(256, FIND_GEMM3_MIN_WGS) void gemm3_kernel(const Ge
 			load_frags(sb, 3, af1, bf1);
 			// scalar preparation of the next publish / issue, under the MFMAs below and BEFORE the barrier
 			const bool more = consumed + 1 < total;
-			const bool do_issue = more && pt < t1 && !(ablate & 1);
+			const bool do_issue = more && pt < t1;
 			if (do_issue) issue_prepare();
 			const int ns = (cs == 2) ? 0 : cs + 1;
 			const char* nsb = smem + ns * STAGE;
@@ -280,9 +276,7 @@ __global__ __launch_bounds__(256, FIND_GEMM3_MIN_WGS) void gemm3_kernel(const Ge
 			mfma_all(af0, bf0);
 			// ---- early barrier
 			if (more) {
-				const unsigned long long c0 = dbg ? __builtin_amdgcn_s_memtime() : 0;
 				asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-				const unsigned long long c1 = dbg ? __builtin_amdgcn_s_memtime() : 0;
 				if (ahead <= 0) {
 					FIND_WAIT_VMCNT(0);
 				} else if (since_epi < 2) {
@@ -292,7 +286,6 @@ __global__ __launch_bounds__(256, FIND_GEMM3_MIN_WGS) void gemm3_kernel(const Ge
 				}
 				__builtin_amdgcn_s_barrier();
 				++since_epi;
-				if (dbg) { const unsigned long long c2 = __builtin_amdgcn_s_memtime(); c_wait += c2 - c1; c_lgkm += c1 - c0; }
 			}
 			__builtin_amdgcn_sched_barrier(0);
 			mfma_k(af1, bf1, 0);  // issued straight after the barrier: depends on nothing new
@@ -318,7 +311,6 @@ __global__ __launch_bounds__(256, FIND_GEMM3_MIN_WGS) void gemm3_kernel(const Ge
 		// ---- epilogue: buffer stores.  Address = SRD base (tile origin) + per-lane voffset (fixed) + SGPR soffset +
 		// immediate, so no per-store address arithmetic; the SRD's size is the number of VALID bytes of the tile, so rows
 		// past the end of a foot are dropped by the hardware bounds check instead of exec masking.
-		const unsigned long long ce0 = dbg ? __builtin_amdgcn_s_memtime() : 0;
 		{
 			float* ytile = g.y + (int64_t)foot * g.y_foot_stride + (int64_t)v0 * ldy;
 			const int valid_rows = min(BM, V - v0);
@@ -335,16 +327,11 @@ __global__ __launch_bounds__(256, FIND_GEMM3_MIN_WGS) void gemm3_kernel(const Ge
 						if constexpr (EPI == EPI_MASK) val = (mv[mi][ni][r] > 0.f) ? val : 0.f;
 						const int soff = ((mi * 32 + 8 * (r >> 2)) * ldy) * 4;       // wave-uniform
 						const int ioff = ((r & 3) * ldy + ni * 32) * 4;
-						if (!(ablate & 2)) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, val), rsrc, voff + ioff, soff, 0);
+						__builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, val), rsrc, voff + ioff, soff, 0);
 					}
 		}
-		if (dbg) c_epi += __builtin_amdgcn_s_memtime() - ce0;
 		since_epi = 0;
 		if (++tif == tpf) { tif = 0; ++foot; }
-	}
-	if (dbg && tid == 0) {
-		unsigned long long* o = dbg + (size_t)blockIdx.x * 4;
-		o[0] = __builtin_amdgcn_s_memtime() - c_start; o[1] = c_wait; o[2] = c_epi; o[3] = c_lgkm;
 	}
 }
 

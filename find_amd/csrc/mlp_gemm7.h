@@ -1,5 +1,5 @@
 // gemm7_kernel: the K = 256 Linear layer in bf16x3 arithmetic (fp32-faithful on the bf16 matrix pipe: mlp_gemm6.h says what that is and
-// why its error is that of fp32 accumulation alone), built around what bounded gemm6 (tools/ablate_x3.py: of its 93 us at the C2 shape,
+// why its error is that of fp32 accumulation alone), built around what bounded gemm6 (ablation runs of round 4: of its 93 us at the C2 shape,
 // 34 were the A loads -- every lane reading its own row: 32 cache lines per load instruction, four column groups re-reading and
 // RE-SPLITTING the same rows --, 17 the LDS traffic of the weight fragments, 15 the split arithmetic; the matrix pipe 50 % busy):
 //   * THE WEIGHTS STAY IN REGISTERS.  A wave owns 16 columns of the output for its whole life and holds those rows of W for all of K
@@ -36,8 +36,7 @@ constexpr int G7_BUF = 3 * G7_PLANE;           // 52 224 B
 constexpr int GEMM7_LDS = 2 * G7_BUF;          // 104 448 B
 constexpr int GEMM7_NW = 8;
 
-// ABL: profiling only (tools/ablate_x3.py; results are wrong under every bit): 1 = no split / LDS writes, 2 = no fragment reads after a unit's
-// first, 4 = no activation loads after the prologue, 8 = no stores
+// (The second template parameter is unused and always 0: it keeps the kernels' names, which the benchmark's records carry.)
 // VIRT ("bcast_fold", mlp.hip): the layer behind a head's broadcast first layer forms that layer's output h1 = relu(P[v] + bias[foot]) itself
 // instead of reading n_feet x V x 1 KB of it from HBM -- from the V x 256 product P (a0 / mask with foot stride 0: L2) and the foot's bias
 // row: EPI_BIAS_RELU: the A operand, two packed adds and four max per staged row in front of its split (g.va_bias); EPI_MASK: the ReLU
@@ -51,7 +50,7 @@ constexpr int GEMM7_NW = 8;
 // run that covers a whole tile writes zeros to slot 1); the per-foot column sums go through 16-lane DPP sums into an LDS table
 // [foot][this workgroup's 128 columns] (each wave its own columns, in unit order) and out to g.cs_out [range][foot][256] at the end.
 // Every sum in a fixed order: bit-reproducible.
-template <int EPI, int ABL = 0, bool VIRT = false, bool FSUM = false>
+template <int EPI, int = 0, bool VIRT = false, bool FSUM = false>
 __global__ __launch_bounds__(GEMM7_NW * 64, 1) void gemm7_kernel(const Gemm2Args g) {
 	static_assert(!VIRT || EPI != EPI_NONE, "gemm7_kernel: a virtual operand needs the epilogue it belongs to");
 	static_assert(!FSUM || (VIRT && EPI == EPI_MASK), "gemm7_kernel: the folded foot sum belongs to the virtual-mask dX GEMM");
@@ -111,9 +110,8 @@ __global__ __launch_bounds__(GEMM7_NW * 64, 1) void gemm7_kernel(const Gemm2Args
 	};
 	auto unit_rsrc = [&](int uu) -> __amdgpu_buffer_rsrc_t {
 		// (a unit past the end of the range: size 0, every load comes back as zeros; so do the rows past the end of a foot)
-		const int ua = FIND_ABL(g.ablate, 512) ? u0 : uu;   // profiling only: every unit reads the range's first rows (served by L2)
 		int foot, v0;
-		decode(ua, foot, v0);
+		decode(uu, foot, v0);
 		const int valid = uu < u1 ? min(32, V - v0) : 0;
 		return make_srd(g.a0 + (int64_t)foot * g.a_foot_stride + (int64_t)v0 * lda, valid * lda * 4);
 	};
@@ -201,8 +199,6 @@ __global__ __launch_bounds__(GEMM7_NW * 64, 1) void gemm7_kernel(const Gemm2Args
 	}
 
 	int cb = 0;
-	unsigned long long t_bar = 0, t_loop = 0;
-	const unsigned long long t_start = FIND_DBG(g.dbg) ? __builtin_amdgcn_s_memtime() : 0ull;
 
 	// lane (row i16 of block rb, quarter h4) holds columns col0 + 4 h4 .. + 3 of its row in the four registers of acc[rb]
 	f32x4 acc[2];
@@ -216,8 +212,7 @@ __global__ __launch_bounds__(GEMM7_NW * 64, 1) void gemm7_kernel(const Gemm2Args
 		acc[0] = t; acc[1] = t;
 	};
 	struct OutTile { __amdgpu_buffer_rsrc_t y, m; };
-	auto out_tile = [&](int uq) -> OutTile {
-		const int uu = FIND_ABL(g.ablate, 1024) ? u0 : uq;   // profiling only: every unit's block goes to the range's first rows
+	auto out_tile = [&](int uu) -> OutTile {
 		int foot, v0;
 		decode(uu, foot, v0);
 		const int nbytes = min(32, V - v0) * ldy * 4;
@@ -285,9 +280,7 @@ __global__ __launch_bounds__(GEMM7_NW * 64, 1) void gemm7_kernel(const Gemm2Args
 	// Unit u: multiply it (buffer cb).  Under its 96 MFMAs: split and store unit u + 1 from `slot` (one PAIR of values per k-step: nine
 	// VALU instructions against twelve MFMAs), refill `slot` with unit u + 3, store the previous unit's blocks (`first`: there is none).
 	auto unit_body = [&](int u, u4 (&slot)[4], bool first) {
-		const unsigned long long tb0 = FIND_DBG(g.dbg) ? __builtin_amdgcn_s_memtime() : 0ull;
 		lds_barrier();   // unit u is complete in buffer cb; nobody reads buffer cb ^ 1 (unit u - 1) any more (the loads in flight stay in flight)
-		const unsigned long long tb1 = FIND_DBG(g.dbg) ? __builtin_amdgcn_s_memtime() : 0ull;
 		const char* buf = smem + cb * G7_BUF;
 		char* other = smem + (cb ^ 1) * G7_BUF;
 		const __amdgpu_buffer_rsrc_t rs2 = unit_rsrc(u + 3);
@@ -317,7 +310,7 @@ __global__ __launch_bounds__(GEMM7_NW * 64, 1) void gemm7_kernel(const Gemm2Args
 			// The further a wave is into its unit, the lower its priority: the two waves of a SIMD then SHARE the matrix pipe.  (The
 			// arbiter prefers the older wave: without this, wave w ran its k loop at full speed and waited at the barrier -- a quarter of the
 			// kernel's time -- while wave w + 4 ran the rest of its own alone, with every stall of a lone wave exposed.)
-			if (h == 0 && !FIND_ABL(g.ablate, 16)) {   // (the switch exists in the laboratory build only)
+			if (h == 0) {
 				if (row == 0) __builtin_amdgcn_s_setprio(3);
 				else if (row == 1) __builtin_amdgcn_s_setprio(2);
 				else if (row == 2) __builtin_amdgcn_s_setprio(1);
@@ -326,46 +319,41 @@ __global__ __launch_bounds__(GEMM7_NW * 64, 1) void gemm7_kernel(const Gemm2Args
 			if (s + 1 < 8) {
 #pragma unroll
 				for (int rb = 0; rb < 2; ++rb) {
-					if constexpr (!(ABL & 2)) { a1[nx][rb] = frag(buf, 0, s + 1, rb); a2[nx][rb] = frag(buf, 1, s + 1, rb); a3[nx][rb] = frag(buf, 2, s + 1, rb); }
-					else { a1[nx][rb] = a1[cu][rb]; a2[nx][rb] = a2[cu][rb]; a3[nx][rb] = a3[cu][rb]; }
+					a1[nx][rb] = frag(buf, 0, s + 1, rb); a2[nx][rb] = frag(buf, 1, s + 1, rb); a3[nx][rb] = frag(buf, 2, s + 1, rb);
 				}
 			}
 			// VMEM operations behind the load of slot[row] when it is needed (buffer loads and stores complete in order): the rest of its own
 			// unit's, those of the unit after it and this unit's so far -- at least 7 in every unit of the pipeline (10-11 in the steady
 			// state: two units of loads stay in flight)
-			if (h == 0 && !(ABL & 1)) {
+			if (h == 0) {
 				FIND_VM_WAIT(slot[row], 7);
 				if constexpr (VA) q.begin_virtual(slot[row], vab);
 				else q.begin(slot[row]);
 			}
 			// smallest terms first
 			mm(B1[s], a3[cu][0], acc[0]); mm(B1[s], a3[cu][1], acc[1]);
-			if constexpr (!(ABL & 1)) q.stage(h, 0);
+			q.stage(h, 0);
 			__builtin_amdgcn_sched_barrier(0);
 			mm(B3[s], a1[cu][0], acc[0]); mm(B3[s], a1[cu][1], acc[1]);
 			__builtin_amdgcn_sched_barrier(0);
 			mm(B2[s], a2[cu][0], acc[0]); mm(B2[s], a2[cu][1], acc[1]);
-			if constexpr (!(ABL & 1)) q.stage(h, 1);
+			q.stage(h, 1);
 			__builtin_amdgcn_sched_barrier(0);
 			mm(B1[s], a2[cu][0], acc[0]); mm(B1[s], a2[cu][1], acc[1]);
-			if (h == 1 && !first && s >= 4 && !(ABL & 8)) {
+			if (h == 1 && !first && s >= 4) {
 				if constexpr (EPI == EPI_MASK) { if (s == 5) FIND_VM_WAIT(mv[0], 2); else FIND_VM_WAIT(mv[1], 3); }   // (behind it: the other mask load, this unit's loads and store so far)
 				store_block(prev, (s - 4) >> 1);
 			}
 			__builtin_amdgcn_sched_barrier(0);
 			mm(B2[s], a1[cu][0], acc[0]); mm(B2[s], a1[cu][1], acc[1]);
-			if constexpr (!(ABL & 1)) q.stage(h, 2);
+			q.stage(h, 2);
 			__builtin_amdgcn_sched_barrier(0);
 			mm(B1[s], a1[cu][0], acc[0]); mm(B1[s], a1[cu][1], acc[1]);
 			if (h == 1) {
-				if constexpr (!(ABL & 1)) { write_plane(other, q, row, 0); write_plane(other, q, row, 1); write_plane(other, q, row, 2); }
-				if constexpr (!(ABL & 4)) load_row(rs2, slot, row);   // unit u + 3: on its way for two units
+				write_plane(other, q, row, 0); write_plane(other, q, row, 1); write_plane(other, q, row, 2);
+				load_row(rs2, slot, row);   // unit u + 3: on its way for two units
 			}
 			__builtin_amdgcn_sched_barrier(0);
-		}
-		if (FIND_DBG(g.dbg)) {   // profiling only (tools/prof_x3.py, FIND_DBG): ticks of wave 0 at the barrier / in the k loop
-			const unsigned long long te1 = __builtin_amdgcn_s_memtime();
-			t_bar += tb1 - tb0; t_loop += te1 - tb1;
 		}
 		cb ^= 1;
 	};
@@ -395,10 +383,6 @@ __global__ __launch_bounds__(GEMM7_NW * 64, 1) void gemm7_kernel(const Gemm2Args
 	if constexpr (FSUM) {   // the per-foot column sums of this range: cs_out [range = pair][foot][256]
 		float* out = g.cs_out + (int64_t)pair * nf * 256 + ((b >> 3) & 1) * 128 + wave * 16;
 		for (int k = lane; k < nf * 16; k += 64) out[(k >> 4) * 256 + (k & 15)] = cs_lds[(k >> 4) * 128 + wave * 16 + (k & 15)];
-	}
-	if (FIND_DBG(g.dbg) && tid == 0) {
-		g.dbg[blockIdx.x * 4 + 0] = __builtin_amdgcn_s_memtime() - t_start;
-		g.dbg[blockIdx.x * 4 + 1] = t_bar; g.dbg[blockIdx.x * 4 + 2] = 0; g.dbg[blockIdx.x * 4 + 3] = t_loop;
 	}
 }
 

@@ -104,7 +104,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void r
 		bool crossed = false;
 		int n_at = 0, s_at = 0;
 		float a_at = 1.0f, f_at = INFINITY;
-		int n_eval = 0;
 		float bz = INFINITY, bd = 0.f, bw0 = 0.f, bw1 = 0.f, bw2 = 0.f;
 		int bf = -1;
 		float front = 0.0f, front1 = 0.0f;   // every face not yet evaluated has its fragments behind `front`; front1: one slab further
@@ -184,7 +183,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void r
 			}
 			// a pixel that holds its K nearest (and its colour) in front of everything from this batch on needs nothing more
 			const bool fin = !in_img || ((!want_sil || c_lt >= K) && (!want_rgb || bz < front));
-			const bool need = (early ? !fin : in_img) && !FIND_ABL(a.ablate, 4);
+			const bool need = (early ? !fin : in_img) && true;   // (the && keeps `early` a branch around the batch, as the kernel was tuned: alone, the ?: becomes a select inside it)
 			const int nb = stage(e_lane);
 			const int slab_v = (int)(e_lane >> 24);   // (sorted lists are binned: position in the batch = lane)
 			// positions of the batch at which a new slab begins (bit p: entry p starts one), plus the position behind the batch's last entry
@@ -206,7 +205,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void r
 				const bool inb_a = need & (px <= bx4.z) & (px >= bx4.x) & (py <= by4.z) & (py >= by4.x);
 				const bool inb_b = two & need & (px <= bx4.w) & (px >= bx4.y) & (py <= by4.w) & (py >= by4.y);
 				if (__ballot(inb_a | inb_b) == 0ull) continue;
-				if (FIND_ABL(a.ablate, 64)) n_eval += two ? 2 : 1;
 				Frag2 fr2;
 				eval_pair(blk, px, py, &fr2);   // (every lane: the ones outside the bboxes compute along and are masked out below)
 				const float2 fid = *reinterpret_cast<const float2*>(blk + 54);   // the two face indices
@@ -255,7 +253,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void r
 				alpha = a_at;
 				thr = __uint_as_float(__float_as_uint(f_at) - 1u);   // the largest float in front of f_at (FLT_MAX for +inf)
 			}
-			const bool hard = in_img && crossed && n_at > K && !FIND_ABL(a.ablate, 2);
+			const bool hard = in_img && crossed && n_at > K;
 			const unsigned long long hard_m = __ballot(hard);
 			if (hard_m) {
 				// ---- second sweep: the band candidates of the hard pixels.  Faces of slab s have their fragments in [edge of s, front of s + 2):
@@ -274,7 +272,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void r
 					b_first = (int)__popcll(__ballot(lane >= 1 && lane < n_batches && s0 < s_lo));   // batch b goes by when batch b + 1 still starts in front of s_lo
 					b_last = (int)__popcll(__ballot(lane < n_batches && s0 <= s_hi)) - 1;
 				}
-				int n_eval2 = 0, n_staged2 = 0, n_items2 = 0;
 				// this lane's own slab range (an unsorted list carries no slabs: every face)
 				const int my_lo = sorted ? s_prev - 1 : -0x7FFFFFFF, my_hi = sorted ? s_at - 1 : 0x7FFFFFFF;
 				float* const recw = &rec[wave][0];                       // records of this sweep: FLAT, piece k of record j at [REC_DW j + 4 (k ^ (j & 7))] (the swizzle spreads the 16-byte staging writes of neighbouring lanes over the banks)
@@ -297,7 +294,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void r
 						for (int k = 0; k < REC_F4; ++k) { float4 q = src[k]; if (k == 6) q.w = __int_as_float((int)e); d[k ^ (pos & 7)] = q; }   // (the list entry in the id slot: slab << 24 | face)
 					}
 					wave_lds_sync();
-					n_staged2 += nb;
 					int j = 0;
 					for (;;) {
 						// queue (pixel, face) pairs until 64 wait or the batch's faces are through
@@ -332,16 +328,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void r
 							const unsigned zb = __float_as_uint(fr.pz_clip + 0.0f);
 							__hip_atomic_fetch_min(&bcnt[64 + hl], zb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
 							__hip_atomic_fetch_max(&bcnt[128 + hl], zb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-							if (slot < (unsigned)KN_CAP && !FIND_ABL(a.ablate, 1)) {
+							if (slot < (unsigned)KN_CAP) {
 								const int64_t o = (int64_t)slot * 64 + hl;
 								wz0[o] = fr.pz_clip;
 								wq0[o] = 1.0f - silhouette_prob(fr.inside ? -fr.dist : fr.dist, inv_sigma);
 								wf0[o] = r.f;
 							}
 						}
-						n_items2 += count;
 						q_head = (q_head + count) & 127; q_n -= count;
-						++n_eval2;
 						wave_lds_sync();
 					}
 				}
@@ -350,26 +344,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void r
 				const float z_lo = __uint_as_float(bcnt[64 + lane]), z_hi = __uint_as_float(bcnt[128 + lane]);
 				wave_lds_sync();
 				const int rank = K - n_prev;   // 1-based rank of the K-th nearest inside the band
-				const bool solve = hard && nbnd <= KN_CAP && nbnd > rank && !FIND_ABL(a.ablate, 1);   // (nbnd == n_at - n_prev > rank by construction)
+				const bool solve = hard && nbnd <= KN_CAP && nbnd > rank;   // (nbnd == n_at - n_prev > rank by construction)
 				{
 					const unsigned long long trunc = __ballot(hard && nbnd > KN_CAP);
-					int wave_max = hard ? nbnd : 0;   // diagnostics: [5] largest band seen, [26] band candidates in all
-					if (FIND_ABL(a.ablate, 64)) {
-						int tb2 = hard ? nbnd : 0;
-#pragma unroll
-						for (int d = 1; d < 64; d <<= 1) tb2 += __shfl_xor(tb2, d, 64);
-						if (lane == 0) atomicAdd(&a.flags[26], tb2);
-					}
+					int wave_max = hard ? nbnd : 0;   // diagnostics: [5] largest band seen
 #pragma unroll
 					for (int d = 1; d < 64; d <<= 1) wave_max = max(wave_max, __shfl_xor(wave_max, d, 64));
 					if (lane == 0) {   // diagnostics: [4] pixels that needed the second sweep; [1] of those, left unresolved
 						atomicAdd(&a.flags[4], (int)__popcll(hard_m));
 						atomicMax(&a.flags[5], wave_max);
 						if (trunc) atomicAdd(&a.flags[1], (int)__popcll(trunc));
-						if (FIND_ABL(a.ablate, 64)) {   // [27] second-sweep evaluations (64 pairs each), [28] tiles that took it, [29] (pixel, face) pairs queued, [30] faces staged, [31] the tiles' list lengths
-							atomicAdd(&a.flags[27], n_eval2); atomicAdd(&a.flags[28], 1); atomicAdd(&a.flags[29], n_items2); atomicAdd(&a.flags[30], n_staged2);
-							atomicAdd(&a.flags[31], n_list);
-						}
 					}
 				}
 				if (solve) {
@@ -506,12 +490,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void r
 			}
 		}
 
-		if (FIND_ABL(a.ablate, 64)) {  // diagnostics: [24] (pixel, face) tests issued (64-lane slots, in units of 64), [25] silhouette candidates seen (units of 64)
-			int te = n_eval, tc = in_img ? c_lt + c_a + c_b : 0;
-#pragma unroll
-			for (int d = 1; d < 64; d <<= 1) { te += __shfl_xor(te, d, 64); tc += __shfl_xor(tc, d, 64); }
-			if (lane == 0 && te) { atomicAdd(&a.flags[24], (te + 32) >> 6); atomicAdd(&a.flags[25], (tc + 32) >> 6); }
-		}
 		if (in_img) {
 			const int64_t pix = ((int64_t)img * H + yi) * W + xi;
 			if (want_sil) {

@@ -167,23 +167,17 @@ int find_linear_wgrad(find_ctx* ctx, const float* dz, const float* x, int64_t n_
 					  void* scratch, int64_t scratch_bytes, void* stream);
 
 /* Tuning knobs of a context (no reference counterpart).  Results do not depend on any knob except "mlp_f16" (the precision, below) and the
- * summation order of "reduce_exclusive" = 2, "footsum_fold", "group_head0" / "dw6_group" / "dwpe6" (which kernel sums a weight gradient).  The laboratory -- fault reproducers, superseded kernels kept for A/B runs, per-workgroup timers
- * and the ablation bits under which results are WRONG -- is not in this library: find_amd/build.py builds it from the same sources with
- * -DFIND_DIAG as libfind_hip_diag.so, whose additional keys and entry point include/find_hip_diag.h declares.  Read-only key "diag": 0 here,
- * 1 there.
+ * summation order of "reduce_exclusive" = 2 and "footsum_fold".
  *   "gemm4_min_units" launches with at least this many 32-row x 128-column units use the W-resident kernel on column halves (default 1024)
  *   "gemm4_small"     ... and launches of at least this many 32-row units use it on column quarters (default 64; 0 = never);
  *                     anything smaller, and the two-segment trunk-output gradient, runs on the LDS-DMA ring kernel (gemm3)
- *   "dw2_min_cps", "dw_pe_target"   weight-gradient kernels: shortest row run per workgroup, workgroups of the Fourier layer's launch
- *   "dw_pe_lds_free"  Fourier layer's weight gradient: 1 (default) = dwpe_kernel (no LDS, features regenerated per lane, slabs of 2 pe + 32
- *                     columns; pe_size >= 32), 0 = the LDS-staged kernel of round 1 (A/B runs)
+ *   "dw2_min_cps"     weight-gradient kernels: shortest row run (16-row chunks) per workgroup
  *   "bwd_streams"     0 = backward on the caller's stream only, 1 = weight gradients on the context's side streams (default)
  *   "fwd_streams"     1 = the forward runs the colour head on a side stream beside the displacement head (default), 0 = one stream
  *   "reduce_stream"   1 = slab reduces of the large head layers on their own stream, two alternating slab sets; default 0 (behind their
  *                     weight-gradient launch: measured 0.6 - 0.9 % faster since the weight gradients use no LDS)
  *   "bind_streams"    1 (default) = the first call that forks picks the four side streams among a dozen candidates by probing which
  *                     hardware queue each one shares (see find_ctx_stream_groups); 0 = keep them as created
- *   "r_queue"         which side stream's hardware queue the slab-reduce stream shares: 0 = Q, 1 = T1, 2 = T2 (default, measured best)
  *   "defer_join"      1 = the NEXT find_mlp_bwd, if it is a small per-foot call (the fused-chain path: the texture pass of a train_3d step),
  *                     returns with its weight-gradient kernels still running on the context's side streams; its latent gradients are
  *                     complete on the caller's stream.  The weight-gradient buffers, `scratch` and `ws` of that call must stay untouched
@@ -206,24 +200,19 @@ int find_linear_wgrad(find_ctx* ctx, const float* dz, const float* x, int64_t n_
  *   "footsum_fold"    1 (default; bf16x3, needs "bcast_fold") = the dX GEMM that produces that layer's gradient forms the two sums the backward reads
  *                     of it -- over the feet, and per foot over the rows -- in its epilogue and stores no gradient tensor (gemm7_kernel<.., FSUM>);
  *                     0 = footsum_kernel over the stored tensor.  Same sums in another order (~2e-7 of a gradient's largest entry), deterministic
- *   "group_head0", "pe_on_t2", "direct_w", "dw6_group", "dwpe6"   scheduling / kernel-choice switches of the backward (A/B runs), all default 1:
- *                     the first head layers' weight gradients in the trunk's grouped launch; the Fourier layer's weight gradient on T2; kernels read
- *                     the model's weights without repacked copies; grouped bf16x3 weight gradients; the Fourier layer's on the bf16 pipe
  *   "gemm6_min_units" the same threshold for the bf16x3 kernels (default 1024)
  *   "fused_max_units" calls of at most this many 32-row units (0..1024, default 512) run whole layer chains -- the trunk, trunk + heads of a
  *                     per-foot pass, their dX chains -- in one launch of fused_chain_kernel, and the weight gradients of a chain as one grouped
  *                     launch + one grouped reduce; 0 = one launch per layer at every size
  *   "fused6"          bf16x3 calls run their chains on fused6_kernel (weights pre-split by split_w_kernel into the call's workspace; default 1);
  *                     0 = fused_chain_kernel (fp32 MFMA), as the other precisions
- *   "dw6_wgs"         workgroups (= 256 x 256 slabs) of a dw6_kernel launch: 0 (default) = one per CU, half that inside a backward whose side
- *                     streams are on (it runs beside the next layer's dX GEMM; half the slabs are half the reduce's traffic)
  *   "dw_lds_free"     kernel of the 256 x 256 weight gradients: 1 = dw4_kernel (operands straight from global memory, no LDS, <= 256
  *                     registers; default), 0 = dw2_kernel (LDS-DMA ring, the whole register file of its SIMDs claimed)
  *   "lds_exclusive"   1 = the LDS-DMA ring kernels reserve their CU's whole LDS: round 1's containment of that fault, which turned out
  *                     to be about registers; default 0
  *   "reduce_exclusive" the stress test's hook for that fault (tests/test_gpu_mlp.py): 1 = the slab-reduce kernels reserve their CU's whole LDS;
  *                     2 = they use no LDS and are slow, so that they stay resident beside later weight-gradient kernels; default 0
- *   "ablate"          switches that leave results unchanged (the tests compare them): 16 no s_setprio in gemm4 / gemm7, 32 every column block in
+ *   "ablate"          switches that leave results unchanged (the tests compare them): 16 no s_setprio in gemm4 (gemm7 always sets its wave priorities), 32 every column block in
  *                     the Fourier layer's weight gradient, 128 fused chains always on 32-row tiles.  Any other bit is refused here.
  * The Python binding applies FIND_TUNING="key=value,..." from the environment to every context it creates. */
 

@@ -415,11 +415,13 @@ def test_context_reports_the_device_and_keeps_its_knobs():
 		_lib.set_tuning('no_such_knob', 1)
 	with pytest.raises(RuntimeError, match='out of range'):
 		_lib.set_tuning('bwd_streams', 7)
-	# the laboratory's keys and wrong-result bits exist in libfind_hip_diag.so only (include/find_hip_diag.h)
-	assert _lib.get_tuning('diag') == 0
-	for key in ('gemm7', 'x3_abl', 'dbg', 'dw2_verify'):
+	# the laboratory's keys and wrong-result bits are gone, and so are the keys that selected a measured-and-dropped alternative
+	for key in ('gemm7', 'x3_abl', 'dbg', 'dw2_verify', 'diag', 'cu_reserve', 'dw_pe_lds_free', 'dw_pe_target', 'direct_w', 'dw6_group', 'dwpe6',
+				'group_head0', 'pe_on_t2', 'r_queue', 'group_spf', 'dw6_wgs'):
 		with pytest.raises(RuntimeError, match='unknown key'):
 			_lib.set_tuning(key, 0)
+	with pytest.raises(RuntimeError, match='unknown key'):
+		_lib.get_tuning('diag')
 	with pytest.raises(RuntimeError, match='out of range'):
 		_lib.set_tuning('dw_lds_free', 2)
 	for bits in (1, 2, 4, 8, 512, 1024, 64):

@@ -420,7 +420,7 @@ def test_toes_view_matches_oracle_and_straddling_faces_fail_loudly():
 
 def test_early_exit_and_list_order_change_nothing():
 	"""The rasteriser walks a tile's faces front to back (lists sorted by depth slab) and leaves a pixel -- or the whole tile -- alone once it
-	holds its K nearest candidates in front of everything still to come.  With the exit switched off (find_debug_raster_ablate bit 8) and
+	holds its K nearest candidates in front of everything still to come.  With the exit switched off (find_render_switches bit 8) and
 	with the lists left in face order (bit 16: no slab sort, hence no exit either) the SAME pixels must come out: the same face in front,
 	the same K-nearest set behind every mask value (products of the same factors in another order: equal to rounding), the same
 	bound for the backward; and likewise when a tile finds no room in the list pool and scans the faces itself (bit 256: a pool of 512 entries) -- on a dense mesh at a small size, where every covered pixel has more than K candidates and ties at the K-th

@@ -53,35 +53,6 @@ def views(m, seed=7):
 RASTER_TRAFFIC_C3 = {'raster_kernel': 2 * 649308.6 * 1024 + 616660.7 * 1024, 'sil_bwd_kernel': 2 * 118954.5 * 1024 + 83899.9 * 1024}   # profiles/r05_raster_pmc.txt
 
 
-def raster_counts(verts, fc, Rc, Tc, params):
-	"""(pixel x face tests issued, silhouette candidates) of one forward render: the rasteriser's diagnostic counters (ablation bit 64, which
-	only the laboratory build has: run with FIND_DIAG=1; the product library yields no counts)."""
-	import ctypes
-	from find_amd import _lib
-	if not _lib.DIAG:
-		raster_counts.last_flags = [None] * 64
-		return None, None, None
-	from find_amd._lib import check, current_stream, ptr
-	from find_amd.functional import _faces_i32, _ws
-	L = _lib.lib()
-	N, V = verts.shape[0], verts.shape[1]
-	M, F = Rc.shape[0], fc.shape[0]
-	faces = _faces_i32(fc)
-	keep = int(os.environ.get('RASTER_ABLATE_KEEP', '0'))   # bits to keep while counting (128 = the wave-per-tile kernel)
-	_lib.set_tuning('raster_ablate', 64 | keep)
-	try:
-		ws = _ws(L.find_render_ws_bytes(ctypes.byref(params), N, M, V, F), verts.device)
-		mask = torch.empty(N, M, params.image_h, params.image_w, device=verts.device)
-		check(L.find_render_fwd(ctypes.byref(params), ptr(verts), ptr(faces), 1, None, ptr(Rc), ptr(Tc), N, M, V, F, ptr(mask), None, None, None, ptr(ws),
-								ws.numel(), current_stream(verts.device)), 'find_render_fwd')
-		torch.cuda.synchronize()
-		fl = ws[:256].view(torch.int32).cpu().tolist()
-	finally:
-		_lib.set_tuning('raster_ablate', keep)
-	raster_counts.last_flags = fl
-	return fl[24] * 64, fl[25] * 64, fl[4]
-
-
 def bench_render(n_feet, n_views, size, want_image, cpu=None):
 	v, f = synthetic.template(6890)
 	g = torch.Generator().manual_seed(0)
@@ -106,7 +77,6 @@ def bench_render(n_feet, n_views, size, want_image, cpu=None):
 		loss.backward()
 
 	ms_f, ms_fb = gpu_ms(fwd), gpu_ms(fwdbwd)
-	tests, cands, over_px = raster_counts(verts, fc, Rc, Tc, params)
 	px = n_feet * n_views * size * size
 	images = n_feet * n_views
 	F = f.shape[0]
@@ -114,9 +84,6 @@ def bench_render(n_feet, n_views, size, want_image, cpu=None):
 	out = dict(path=f'render+{"phong+" if want_image else ""}silhouette fwd+bwd', workload=f'{n_feet} feet x {n_views} views @{size}^2, V=6890 F={F}',
 			   ms_fwd=ms_f, ms_fwd_bwd=ms_fb, vertices_views_per_s=n_feet * 6890 * n_views / (ms_fb * 1e-3), mpix_per_s_fwd=px / ms_f / 1e3,
 			   bytes_algorithmic=alg, achieved_GBs_fwd=alg / (ms_f * 1e-3) / 1e9, hbm_frac_fwd=alg / (ms_f * 1e-3) / 1e9 / HBM_PEAK_GBS,
-			   pixel_face_tests=tests, tests_per_s_fwd=None if tests is None else tests / (ms_f * 1e-3), silhouette_candidates=cands, pixels_over_K=over_px,
-			   candidate_list_bytes=None if cands is None else 8 * cands, lane_efficiency=None if cands is None else cands / max(tests, 1),
-			   tiles_left_early=raster_counts.last_flags[26], tie_fixup_pixels=raster_counts.last_flags[7], pool_entries=raster_counts.last_flags[6],
 			   hbm_traffic_bytes_fwd_launch=RASTER_TRAFFIC_C3['raster_kernel'] if (size == 256 and n_feet == 16 and n_views == 4 and not want_image) else None,
 			   bound='VALU (pixel x face fragment math; lists in depth order let a wave leave when its pixels hold their K nearest), then HBM traffic of the '
 					 'per-pixel candidate lists (8 B per candidate, written once, read ~3x by the K-nearest pass); HBM floor of the fused output %.1f us' % (alg / (HBM_PEAK_GBS * 1e9) * 1e6))

@@ -1,11 +1,11 @@
 #!/bin/bash
 # isolated durations of the Fourier weight-gradient kernel: serial backward (no side streams) under the tracer; usage: run_dwpe_iso.sh [extra FIND_TUNING ...]
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}; O=$R/gpurun_out/dwpe; mkdir -p $O; cd /tmp; export TMPDIR=/tmp
-for k in "${@:-dw_pe_lds_free=1}"; do
-export FIND_TUNING=$k,bwd_streams=0 FIND_DEFER_WGRADS=0 FIND_OVERLAP_CHAMFER=0
+for k in "${@:-}"; do
+export FIND_TUNING=${k:+$k,}bwd_streams=0 FIND_DEFER_WGRADS=0 FIND_OVERLAP_CHAMFER=0
 rm -rf $O/iso
 rocprofv3 --kernel-trace --output-format csv -d $O/iso -- python3 $R/bench.py --steps 10 --warmup 5 --no-cpu-baseline --headline-only > $O/iso.log 2>&1
-echo "== $k"
+echo "== ${k:-defaults}"
 python3 - <<PY
 import csv, glob, collections
 for f in glob.glob('$O/iso/*/*kernel_trace.csv'):
