@@ -1,4 +1,5 @@
-// C-ABI: find_mlp_fwd / find_mlp_bwd  -- launch sequences over the kernels in mlp_kernels.h.
+// C-ABI: find_mlp_fwd / find_mlp_bwd  -- launch sequences over the kernels in mlp_kernels.h: dims + workspaces, launches, forward,
+// backward, entry points (the context, its streams and the fork / join of a call: mlp_ctx.h).
 // Replaces NeuralDisplacementField.forward (reference src/model/model.py:393-453) and its autograd backward.
 #include "mlp_dw2.h"
 #include "mlp_dw4.h"
@@ -12,6 +13,7 @@
 #include "mlp_gemm4.h"
 #include "mlp_fused.h"
 #include "mlp_fused6.h"
+#include "mlp_ctx.h"
 
 namespace find {
 namespace mlp {
@@ -123,308 +125,171 @@ static void carve_fwd(const find_mlp_params* p, const Dims& d, bool save, void* 
 	o->bytes = c.off;
 }
 
-}  // namespace mlp
-}  // namespace find
+// row splits of a slab-producing launch: about `target` workgroups over all feet, cps 32-row chunks each
+static void split_policy(int64_t n_feet, int64_t V, int* spf, int* cps, int64_t target = 128) {
+	const int64_t cpf = cdiv(V, 32);
+	int64_t s0 = std::max<int64_t>(1, std::min<int64_t>(cpf, cdiv(target, n_feet)));
+	*cps = (int)cdiv(cpf, s0);
+	*spf = (int)cdiv(cpf, *cps);
+}
 
-// Per-device state of the MLP entry points (find_hip.h: find_ctx_create).  Nothing below is process-global.
-enum { K_GEMM2_PE = 0, K_GEMM3_RELU, K_GEMM3_MASK, K_GEMM3_NONE, K_GEMM4_4_RELU, K_GEMM4_4_MASK, K_GEMM4_4_NONE, K_GEMM4_2_RELU, K_GEMM4_2_MASK,
-	   K_GEMM4_2_NONE, K_GEMM5_RELU, K_GEMM5_MASK, K_GEMM5_NONE, K_GEMM7_RELU, K_GEMM7_MASK, K_GEMM7_NONE, K_DW2, K_DW3, K_DW6, K_DW6G, K_FUSED, K_FUSED2, K_FUSED6, K_FUSED6_2, K_DW2G, K_REDUCE, K_GEMM5_RELU_H, K_GEMM5_MASK_H, K_DW3_H, K_GEMM5_RELU_V, K_GEMM5_MASK_V, K_DW3_V, K_GEMM7_RELU_V, K_GEMM7_MASK_V, K_DW6_V, K_GEMM7_MASK_VF, K_COUNT };
-constexpr int N_SIDE = 4;       // internal streams: 0 = q (large head layers' dW), 1 / 2 = first head layers + trunk layers, 3 = slab reduces
-constexpr int N_EVENTS = 512;   // event ring: an MLP call with 3 x 8 layers uses ~170; checked per call
-
-struct find_ctx {
-	int device = 0;
-	int num_cus = 256;
-	int lds_bytes = 160 * 1024;   // largest dynamic LDS one workgroup may ask for on this device
-	// knobs (find_hip.h: find_ctx_set)
-	int ablate = 0;               // result-preserving switches (MLP_SWITCHES, common.h)
-	int64_t gemm4_min_units = 1024;
-	int gemm4_small = 64;         // column-quarter gemm4 for launches of at least this many 32-row units (0: never)
-	int gemm5_min_units = 1024;
-	int gemm6_min_units = 1024;
-	int mlp_f16 = 0;              // default precision of calls that do not name one
-	int fused_max_units = 512;    // chains of layers over at most this many 32-row tiles run as ONE fused_chain_kernel launch (0: never)
-	int fused6 = 1;               // bf16x3 calls run their chains on fused6_kernel (0: the fp32-MFMA chain, as the other precisions)
-	int dw2_min_cps = 8;          // at least this many 16-row chunks per dw2 workgroup (4: 2.257, 8: 2.243, 12: 2.266 ms/step at C2)
-	int dw_lds_free = 1;          // 256 x 256 weight gradients: 1 = dw4_kernel (no LDS, <= 256 registers), 0 = dw2_kernel (LDS-DMA ring, whole register file claimed)
-	int lds_exclusive = 0;        // 1 = the LDS-DMA ring kernels reserve the whole LDS of their CU: round 1's containment of the co-residence fault, which
-	                              // round 2 showed to be about registers, not LDS (see "Co-residence" below); off by default now
-	int reduce_exclusive = 0;     // diagnosis only: 1 = the slab reduce (16 KB of LDS) reserves its CU's whole LDS; 2 = LDS-free, slow reduce: the stress
-	                              // configuration for the co-residence fault (long-lived foreign waves beside the weight-gradient kernels)
-	int bwd_streams = 1;          // weight gradients on the side streams
-	int fwd_streams = 1;          // colour head on a side stream beside the displacement head
-	int reduce_stream = 0;        // 1 = slab reduces of the large head layers on their own stream R (two alternating slab sets): what the LDS-ring weight
-	                              // gradient needed (its reduce only got a CU when a ring workgroup retired); with dw4_kernel the reduce behind its
-	                              // launch on Q is 0.6 - 0.9 % faster (train_3d 3.245 -> 3.225 ms, C2 2.220 -> 2.199), so off by default
-	int bind_streams = 1;         // 0 = keep the side streams as created
-	int defer_join = 0;           // read by the next find_mlp_bwd: leave the weight-gradient side streams running behind the call (find_hip.h)
-	int act16 = 1;                // in the opt-in fp16 mode the heads' hidden activations and their gradients are STORED as fp16 at the large
-	                              // shared-template shapes (use_act16): those layers are HBM-bound, and the matrix pipe rounds them to fp16 anyway
-	int bcast_fold = 1;           // inside act16 the broadcast first head layer's output is formed by its readers instead of stored (use_fold)
-	int footsum_fold = 1;         // the foot sums of a shared template's first-layer dZ are formed inside the dX GEMM that produces it (mlp_gemm7.h FSUM)
-	// internal streams / events
-	hipStream_t side[N_SIDE] = {nullptr, nullptr, nullptr, nullptr};
-	bool side_bound = false;      // the side streams have been chosen against the hardware queue of a caller's stream (bind_side_streams)
-	hipEvent_t ev[N_EVENTS];
-	int n_events = 0;
-	int next = 0;
-	int events_per_call_max = 0;
-	hipEvent_t pend_ev[N_SIDE] = {nullptr, nullptr, nullptr, nullptr};   // end of the deferred work on each side stream
-	bool pend[N_SIDE] = {};       // side stream k carries deferred work nobody has waited for yet
-	bool attr_done[K_COUNT] = {};
-	// how the last forward calls that saved a workspace stored the heads' activations (act16): the backward of a workspace follows its
-	// forward's decision even if a knob was turned in between (ring of the last 16; a workspace not found falls back to the rule)
-	struct Act16Note { const void* ws; bool a16; bool fold; };
-	Act16Note act16_notes[16] = {};
-	int act16_next = 0;
-	// set per call
-	bool f16 = false;
-	bool x3 = false;              // this call runs its 256 -> 256 layers as bf16x3 (fp32-faithful on the bf16 matrix pipe, mlp_gemm6.h)
+// Backward scratch.
+struct BwdWs {
+	float* Tt[FIND_MAX_LAYERS];  // transposed trunk weights (layers >= 1)
+	float* Dt[FIND_MAX_LAYERS];  // transposed disp-head weights (layer 0: main block)
+	float* Ct[FIND_MAX_LAYERS];
+	float* dzD[FIND_MAX_LAYERS];  // one per head layer (as dzT)
+	float* dzC[FIND_MAX_LAYERS];
+	float* dzT[FIND_MAX_LAYERS];  // one per trunk layer: the dX chain never waits for the side stream's readers
+	float* pw;    // dW partial slabs
+	float* pb;    // bias partial slabs
+	float* pw_t[4];  // slab sets: [0] aliases pw / pb (stream q), [1], [2] the trunk's side streams, [3] alternates with [0] on q
+	float* pb_t[4];
+	float* Sd;    // (n_feet,256) per-foot column sums of the disp head's first-layer dZ
+	float* Sc;
+	float* zsD;   // shared template: (V,256) sum over feet of the disp head's first-layer dZ
+	float* zsC;
+	float* fs1D;  // footsum_fold: the second partial sum of gemm7_kernel<.., FSUM> (the first lands in zsD / zsC)
+	float* fs1C;
+	float* pS;    // [nblk_fs][n_feet][256] partial per-foot column sums (disp head)
+	float* pS2;   // same for the colour head: the reduces run on the side stream, so the heads cannot share one
+	int nblk_fs;
+	float* pwo[2];  // final-layer partials
+	float* pbo[2];
+	int nblk_out;
+	int64_t max_split;
+	float* grp_pw;   // small calls: slabs of the grouped weight-gradient launch, [job][slab][256][256], then the bias rows [job][slab][256]
+	int64_t grp_slabs;  // slabs per job
+	int grp_jobs;
+	void* w6;        // fused6_kernel: the dX chain's weights as fragment-ordered bf16 planes
+	int64_t bytes;
 };
 
-namespace find {
-namespace mlp {
+constexpr int64_t GROUP_MAX_UNITS = 1024;   // largest call (32-row tiles) that may take the fused / grouped small-call path
+constexpr int GROUP_MIN_CPS = 8;            // 16-row chunks per workgroup of a grouped weight gradient, at least
 
-#define FIND_HIP_OK(expr, what)                                                                  \
-	do {                                                                                         \
-		hipError_t _e = (expr);                                                                  \
-		if (_e != hipSuccess) {                                                                  \
-			set_error("%s: %s", what, hipGetErrorString(_e));                                    \
-			return FIND_ELAUNCH;                                                                 \
-		}                                                                                        \
-	} while (0)
+static void carve_bwd(const find_mlp_params* p, const Dims& d, void* scratch, BwdWs* o) {
+	Carver c(scratch);
+	for (int i = 1; i < p->n_trunk; ++i) o->Tt[i] = c.take<float>((int64_t)W * W);
+	for (int i = 0; i < p->n_disp; ++i) o->Dt[i] = c.take<float>((int64_t)W * W);
+	for (int i = 0; i < p->n_col; ++i) o->Ct[i] = c.take<float>((int64_t)W * W);
+	for (int i = 0; i < std::max(p->n_disp, 1); ++i) o->dzD[i] = c.take<float>(d.rows_h * W);
+	for (int i = 0; i < std::max(p->n_col, 1); ++i) o->dzC[i] = c.take<float>(d.rows_h * W);
+	for (int i = 0; i < std::max(p->n_trunk, 1); ++i) o->dzT[i] = c.take<float>(d.rows_t * W);
+	int spf, cps;
+	split_policy(d.n_feet, d.V, &spf, &cps);
+	int64_t ms = d.n_feet * spf;
+	split_policy(1, d.V, &spf, &cps);
+	ms = std::max<int64_t>(ms, spf);
+	o->max_split = ms;
+	// dw2 policy: up to max(#CUs, feet) main slabs + one tail slab per foot, each 256x256
+	const int64_t ms2 = std::max<int64_t>(512, d.n_feet) + d.n_feet + 16;
+	o->pw = c.take<float>(std::max<int64_t>(ms * W * KP0, ms2 * W * W));
+	o->pb = c.take<float>(std::max<int64_t>(ms, ms2) * W);
+	o->pw_t[0] = o->pw; o->pb_t[0] = o->pb;
+	for (int i = 1; i < 4; ++i) {  // trunk layers have matrix inputs (dw2 slabs) except layer 0, which always uses set 0
+		o->pw_t[i] = c.take<float>(ms2 * W * W);
+		o->pb_t[i] = c.take<float>(ms2 * W);
+	}
+	o->Sd = c.take<float>(d.n_feet * W);
+	o->Sc = c.take<float>(d.n_feet * W);
+	o->nblk_fs = (int)cdiv(d.V, FS_ROWS);
+	if (d.shared) {
+		o->zsD = c.take<float>(d.V * W);
+		o->zsC = c.take<float>(d.V * W);
+		o->fs1D = c.take<float>(d.V * W);
+		o->fs1C = c.take<float>(d.V * W);
+	} else {
+		o->zsD = o->zsC = o->fs1D = o->fs1C = nullptr;
+	}
+	// (also without a shared template: the latents-only backward of a frozen network takes its per-foot column sums this way)
+	o->pS = c.take<float>((int64_t)o->nblk_fs * d.n_feet * W);
+	o->pS2 = c.take<float>((int64_t)o->nblk_fs * d.n_feet * W);
+	o->w6 = c.take<char>(chain_w6_bytes(p));
+	o->grp_pw = nullptr; o->grp_slabs = 0; o->grp_jobs = 0;
+	if (cdiv(d.V, 32) * d.feet_t <= GROUP_MAX_UNITS) {
+		// (a shared trunk groups its own layers only: the heads' layers there have n_feet times the rows and keep their own launches)
+		// (round 6: ... and the heads' FIRST layers, whose foot-summed gradient has the trunk's V rows)
+		o->grp_jobs = d.shared ? (p->n_trunk - 1) + 2 : (p->n_trunk - 1) + p->n_disp + p->n_col;
+		o->grp_slabs = std::max<int64_t>(d.feet_t * (cdiv(d.V / 16, GROUP_MIN_CPS) + 1), std::min<int64_t>(d.feet_t * cdiv(d.V / 16, 2), 32));
+		if (o->grp_jobs > 0) o->grp_pw = c.take<float>((int64_t)o->grp_jobs * o->grp_slabs * ((int64_t)W * W + W));
+	}
+	o->nblk_out = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(d.rows_h, 64), 512));
+	for (int i = 0; i < 2; ++i) {
+		o->pwo[i] = c.take<float>((int64_t)o->nblk_out * 3 * W);
+		o->pbo[i] = c.take<float>((int64_t)o->nblk_out * 4);
+	}
+	o->bytes = c.off;
+}
 
-#define FIND_TRY(expr)                    \
-	do {                                  \
-		const int _r = (expr);            \
-		if (_r != FIND_OK) return _r;     \
-	} while (0)
+// ------------------------------------------------------------------------------------------- launches
+// One tile launch of a Linear-shaped kernel: LDS attribute and size (prepare_kernel), the tile arithmetic every such kernel shares, the launch.
+struct TileLaunch { int id; int lds; int rows; int grid; int block; };   // kernel id (attr_done), LDS bytes needed, rows per tile, launch geometry
 
-// Co-residence fault: what it was.
-// Round 1: with a second workgroup of another stream resident on the same CU, dw2_kernel (weight gradient, both MFMA operands through
-// an LDS-DMA ring, one wave per SIMD) produced rare wrong partial tiles -- a rank-1 error of ~1 % in a handful of dW elements, 3 % of the
-// backward passes at 4 x 1002 rows, 13 % at 16 x 6890, every pass when the dX GEMMs ran on gemm3 beside it -- with every vmcnt / barrier of
-// the ring in place.  Launching the LDS-DMA ring kernels with the WHOLE LDS of their CU made it disappear (0 of 500 passes) and was taken
-// for the cure: "an LDS-using neighbour disturbs the ring".  It was a coincidence of which neighbours it kept out.
-// Round 2 (tools/check_determinism.py with the knobs named; numbers = wrong tensors per 150 passes of a 16 x 6890 backward):
-//   * a stress configuration reproduces it in EVERY pass: the slab reduce replaced by an LDS-free, slow one ("reduce_exclusive" = 2),
-//     so that reduces of earlier layers stay resident beside the weight-gradient kernels of later ones: ~850 -- with the LDS reservation
-//     on as well as off (it cannot keep an LDS-free kernel out).  The layers that break are exactly those whose weight-gradient launch
-//     overlaps a running reduce; on one stream ("bwd_streams" = 0): 0.
-//   * not the slabs (a private slab set per weight gradient: same rate); not the ring (every stage of every chunk equals HBM when it is
-//     published AND after the wave has consumed it, 2.35 M stages per run); not barrier timing, DMA in flight, M0 hazards, operand-register
-//     reuse, barrier flavour (each padded / changed: same rate).
-//   * not LDS at all: a four-wave dw4 ("dw4 wide") -- no LDS, no DMA, no barrier, dw2's tile shape read straight from global memory -- breaks the
-//     same way (663), while dw4_kernel, the same code with half the tile per wave, never does (0 in 1450 passes).
-//   * what the victims share is their REGISTER SHAPE: dw2 312, dw2_group 300, dw4 wide 328 registers per lane -- all 256 accumulator
-//     registers (the whole AGPR set) behind fewer than 256 architectural ones, one wave per SIMD.  Every kernel with at most 256 registers
-//     was clean; so was the masked gemm3 when it still took 328 (200 architectural + 128 accumulator registers: 0 in 160 stress passes,
-//     rebuilt with -DFIND_GEMM3_MIN_WGS=1), so the trigger is narrower than "more than 256".  And dw2 UNCHANGED except for its allocation
-//     padded to all 512 registers of the SIMD (FIND_CLAIM_WHOLE_REGISTER_FILE: no foreign wave fits beside it any more): 0 in 600
-//     passes, LDS reservation off.
-// So: a wave that owns the full accumulator set within an allocation of fewer than 512 registers gets wrong register contents when
-// waves of another kernel are allocated on its SIMD.
-// The kernel descriptors are right (dw2: granulated VGPR count 38 = 312 registers, accum_offset 56); whether the silicon, the firmware's
-// wave save / restore or the runtime mishandles such waves cannot be told from inside a kernel (a stand-alone two-kernel program with a
-// 292-register victim ran clean: something else of the step's setting takes part).  The rule adopted, a superset of every shape that
-// broke and enforced by tests/test_host_api.py on the compiler's output: a kernel either fits in 256 registers or claims the whole file.  dw4_kernel (<= 256,
-// two waves per SIMD, no LDS) is the default weight gradient; dw2 / dw2_group / dw3 claim the file; gemm3 is capped at 256 through its
-// launch bounds (the two reproducers -- round 1's dw2 and the wide dw4 -- have been removed since).  The whole-LDS reservation is
-// off by default ("lds_exclusive"): the stress runs are clean without it, and what it really did was keep most neighbours away.
+static int ntiles_of(int64_t V, int rows, int64_t feet) { return (int)((int)cdiv(V, rows) * feet); }
+
 template <typename K>
-static int prepare_kernel(find_ctx* c, int id, K kernel, int need_bytes, int* launch_bytes, bool reserve = true) {
-	const int want = (reserve && c->lds_exclusive) ? c->lds_bytes : need_bytes;
-	if (need_bytes > c->lds_bytes) {
-		set_error("find_mlp: kernel needs %d bytes of LDS, device %d grants %d per workgroup", need_bytes, c->device, c->lds_bytes);
-		return FIND_EINVAL;
-	}
-	if (!c->attr_done[id]) {
-		FIND_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_bytes),
-					"hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
-		c->attr_done[id] = true;
-	}
-	*launch_bytes = want;
+static int launch_tiles(find_ctx* c, K kernel, const TileLaunch& t, Gemm2Args a, int64_t feet, hipStream_t s) {
+	int lds = 0;
+	FIND_TRY(prepare_kernel(c, t.id, kernel, t.lds, &lds));
+	a.tiles_per_foot = (int)cdiv(a.V, t.rows);
+	a.ntiles = (int)(a.tiles_per_foot * feet);
+	hipLaunchKernelGGL(kernel, dim3(t.grid), dim3(t.block), lds, s, a);
 	return FIND_OK;
 }
 
-// Fork / join of one entry-point call onto the context's side streams.  fork_to(k) makes side stream k wait for everything issued on
-// the caller's stream so far; chain(a, b) orders side stream b behind a; join() -- called on EVERY exit path after the first fork,
-// error returns included -- makes the caller's stream wait for every side stream this call touched, so that when the call returns
-// the caller may free or reuse any buffer it passed in (stream-ordered).  Every HIP return code is kept: the first failure is
-// reported by join().  Works under stream capture: a captured call forks and joins the same streams, so the capture stays closed.
-static int bind_side_streams(find_ctx* c, hipStream_t caller);   // (below, with the probe)
+// the runtime epilogue as a compile-time constant: f(std::integral_constant<int, EPI>)
+template <typename F>
+static int with_epi(int epi, F&& f) {
+	if (epi == EPI_BIAS_RELU) return f(std::integral_constant<int, EPI_BIAS_RELU>{});
+	if (epi == EPI_MASK) return f(std::integral_constant<int, EPI_MASK>{});
+	return f(std::integral_constant<int, EPI_NONE>{});
+}
+constexpr int epi_slot(int epi) { return epi == EPI_BIAS_RELU ? 0 : epi == EPI_MASK ? 1 : 2; }   // the kernel ids of a family: .._RELU, .._MASK, .._NONE
 
-struct Fork {
-	find_ctx* c;
-	hipStream_t s;
-	bool on;              // side streams in use for this call
-	bool capturing = false;   // the caller's stream is being captured into a HIP graph
-	bool used[N_SIDE] = {};
-	int n_ev = 0;
-	int rc = FIND_OK;
-
-	Fork(find_ctx* ctx, hipStream_t caller, bool enable) : c(ctx), s(caller), on(enable && ctx->side[0] != nullptr) {
-		hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-		if (hipStreamIsCapturing(caller, &st) == hipSuccess) capturing = st != hipStreamCaptureStatusNone;
-		if (on && !capturing && !ctx->side_bound && ctx->bind_streams) (void)bind_side_streams(ctx, caller);   // (a failed probe keeps the streams as created)
-	}
-	hipStream_t stream(int k) const { return on ? c->side[k] : s; }
-	void fail(hipError_t e, const char* what) {
-		if (e != hipSuccess && rc == FIND_OK) {
-			set_error("%s: %s", what, hipGetErrorString(e));
-			rc = FIND_ELAUNCH;
-		}
-	}
-	hipEvent_t event() {
-		hipEvent_t e = c->ev[c->next];
-		c->next = (c->next + 1) % N_EVENTS;
-		if (++n_ev > N_EVENTS && rc == FIND_OK) {
-			set_error("find_mlp: more than %d events in one call", N_EVENTS);
-			rc = FIND_ELAUNCH;
-		}
-		return e;
-	}
-	void order(hipStream_t from, hipStream_t to) {
-		hipEvent_t e = event();
-		fail(hipEventRecord(e, from), "hipEventRecord");
-		fail(hipStreamWaitEvent(to, e, 0), "hipStreamWaitEvent");
-	}
-	void fork_to(int k) {
-		if (!on) return;
-		order(s, c->side[k]);
-		used[k] = true;
-	}
-	// an event that fires when side stream k has run what was issued so far
-	hipEvent_t mark(int k) {
-		if (!on) return nullptr;
-		hipEvent_t e = event();
-		fail(hipEventRecord(e, c->side[k]), "hipEventRecord");
-		return e;
-	}
-	void wait(int k, hipEvent_t e) {
-		if (on && e) fail(hipStreamWaitEvent(c->side[k], e, 0), "hipStreamWaitEvent");
-	}
-	void chain(int from, int to) {
-		if (!on || from == to) return;
-		// a stream enters the call through a fork from the CALLER's stream first, never only through another side stream: under
-		// stream capture, hipStreamEndCapture (ROCm 7.0 / 7.2) faults on a capture whose parallel stream was pulled in by a stream
-		// that is itself a fork (nested fork); eagerly the extra wait is implied by the one on `from`
-		if (!used[to]) fork_to(to);
-		order(c->side[from], c->side[to]);
-	}
-	int join() {
-		// (also what an earlier call left running there: find_ctx.pend -- streams are FIFO, waiting for this call's end covers it)
-		for (int k = 0; k < N_SIDE; ++k)
-			if ((on && used[k]) || (c->pend[k] && !capturing)) { order(c->side[k], s); used[k] = false; c->pend[k] = false; }
-		c->events_per_call_max = std::max(c->events_per_call_max, n_ev);
-		return rc;
-	}
-	// instead of join(): the side streams this call touched keep running behind it; whoever needs their results waits for pend_ev
-	// (find_ctx_join, or the join() of a later call).  Only the caller may know that nothing reads them before that.
-	int defer() {
-		if (on)
-			for (int k = 0; k < N_SIDE; ++k)
-				if (used[k]) { fail(hipEventRecord(c->pend_ev[k], c->side[k]), "hipEventRecord"); c->pend[k] = true; used[k] = false; }
-		c->events_per_call_max = std::max(c->events_per_call_max, n_ev);
-		return rc;
-	}
-};
-
-static int launch_gemm2_pe(find_ctx* c, Gemm2Args a, int64_t feet, hipStream_t s) {
+static int launch_gemm2_pe(find_ctx* c, const Gemm2Args& a, int64_t feet, hipStream_t s) {
 	constexpr int BM = 64;
-	int lds = 0;
-	const int rc = prepare_kernel(c, K_GEMM2_PE, &gemm2_kernel<BM, AMODE_PE, EPI_BIAS_RELU>, gemm2_lds_bytes<BM>(), &lds);
-	if (rc != FIND_OK) return rc;
-	a.tiles_per_foot = (int)cdiv(a.V, BM);
-	a.ntiles = (int)(a.tiles_per_foot * feet);
-	const int grid = std::min(a.ntiles, c->num_cus);
-	hipLaunchKernelGGL((gemm2_kernel<BM, AMODE_PE, EPI_BIAS_RELU>), dim3(grid), dim3(256), lds, s, a);
-	return FIND_OK;
+	const int grid = std::min(ntiles_of(a.V, BM, feet), c->num_cus);
+	return launch_tiles(c, &gemm2_kernel<BM, AMODE_PE, EPI_BIAS_RELU>, TileLaunch{K_GEMM2_PE, gemm2_lds_bytes<BM>(), BM, grid, 256}, a, feet, s);
 }
 
-template <int BM, int EPI>
-static int launch_gemm3_t(find_ctx* c, Gemm2Args a, int64_t feet, hipStream_t s) {
-	int lds = 0;
-	const int rc = prepare_kernel(c, K_GEMM3_RELU + (EPI == EPI_BIAS_RELU ? 0 : EPI == EPI_MASK ? 1 : 2), &gemm3_kernel<BM, EPI>, gemm2_lds_bytes<BM>(), &lds);
-	if (rc != FIND_OK) return rc;
-	a.tiles_per_foot = (int)cdiv(a.V, BM);
-	a.ntiles = (int)(a.tiles_per_foot * feet);
-	const int grid = std::min(a.ntiles, c->num_cus);
-	hipLaunchKernelGGL((gemm3_kernel<BM, EPI>), dim3(grid), dim3(256), lds, s, a);
-	return FIND_OK;
-}
-
-template <int EPI, int NI, int NW = 8>
-static int launch_gemm4_t(find_ctx* c, Gemm2Args a, int64_t feet, hipStream_t s) {
-	int lds = 0;
-	const int id = (NI == 4 ? K_GEMM4_4_RELU : K_GEMM4_2_RELU) + (EPI == EPI_BIAS_RELU ? 0 : EPI == EPI_MASK ? 1 : 2);
-	const int rc = prepare_kernel(c, id, &gemm4_kernel<EPI, NI, NW>, NI * 32 * 1024, &lds);
-	if (rc != FIND_OK) return rc;
-	a.tiles_per_foot = (int)cdiv(a.V, 32);
-	a.ntiles = (int)(a.tiles_per_foot * feet);
-	constexpr int G = 8 * (8 / NI);  // the column groups of a row range sit 8 blocks apart (same XCD)
-	const int grid = std::max(G, (c->num_cus / G) * G);
-	hipLaunchKernelGGL((gemm4_kernel<EPI, NI, NW>), dim3(grid), dim3(NW * 64), lds, s, a);
-	return FIND_OK;
+static int launch_gemm3(find_ctx* c, int epi, const Gemm2Args& a, int64_t feet, hipStream_t s) {
+	return with_epi(epi, [&](auto E) -> int {
+		constexpr int EPI = decltype(E)::value, BM = 64;
+		const int grid = std::min(ntiles_of(a.V, BM, feet), c->num_cus);
+		return launch_tiles(c, &gemm3_kernel<BM, EPI>, TileLaunch{K_GEMM3_RELU + epi_slot(EPI), gemm2_lds_bytes<BM>(), BM, grid, 256}, a, feet, s);
+	});
 }
 
 template <int NI>
 static int launch_gemm4(find_ctx* c, int epi, const Gemm2Args& a, int64_t feet, hipStream_t s) {
-	if (epi == EPI_BIAS_RELU) return launch_gemm4_t<EPI_BIAS_RELU, NI>(c, a, feet, s);
-	if (epi == EPI_MASK) return launch_gemm4_t<EPI_MASK, NI>(c, a, feet, s);
-	return launch_gemm4_t<EPI_NONE, NI>(c, a, feet, s);
-}
-
-template <int EPI, bool H16 = false, bool VIRT = false>
-static int launch_gemm5_t(find_ctx* c, Gemm2Args a, int64_t feet, hipStream_t s) {
-	int lds = 0;
-	const int id = VIRT ? (EPI == EPI_BIAS_RELU ? K_GEMM5_RELU_V : K_GEMM5_MASK_V)
-				 : H16 ? (EPI == EPI_BIAS_RELU ? K_GEMM5_RELU_H : K_GEMM5_MASK_H) : K_GEMM5_RELU + (EPI == EPI_BIAS_RELU ? 0 : EPI == EPI_MASK ? 1 : 2);
-	const int rc = prepare_kernel(c, id, &gemm5_kernel<EPI, H16, VIRT>, VIRT ? GEMM5_LDS_VIRT : GEMM5_LDS, &lds);
-	if (rc != FIND_OK) return rc;
-	a.tiles_per_foot = (int)cdiv(a.V, 32);
-	a.ntiles = (int)(a.tiles_per_foot * feet);
-	a.tile_major = VIRT ? 1 : 0;   // the feet of a tile side by side: the shared product behind the virtual operand is read from HBM once
-	const int grid = (int)std::min<int64_t>(c->num_cus, cdiv(a.ntiles, GEMM5_NW));
-	hipLaunchKernelGGL((gemm5_kernel<EPI, H16, VIRT>), dim3(grid), dim3(GEMM5_NW * 64), lds, s, a);
-	return FIND_OK;
+	return with_epi(epi, [&](auto E) -> int {
+		constexpr int EPI = decltype(E)::value, NW = 8;
+		constexpr int G = 8 * (8 / NI);  // the column groups of a row range sit 8 blocks apart (same XCD)
+		const int grid = std::max(G, (c->num_cus / G) * G);
+		const int id = (NI == 4 ? K_GEMM4_4_RELU : K_GEMM4_2_RELU) + epi_slot(EPI);
+		return launch_tiles(c, &gemm4_kernel<EPI, NI, NW>, TileLaunch{id, NI * 32 * 1024, 32, grid, NW * 64}, a, feet, s);
+	});
 }
 
 static int launch_gemm5(find_ctx* c, int epi, const Gemm2Args& a, int64_t feet, hipStream_t s, bool h16) {
-	if (h16) {   // fp16-stored A / y / mask (act16): the two epilogues the heads' hidden layers use
-		if (epi == EPI_BIAS_RELU && a.va_bias) return launch_gemm5_t<EPI_BIAS_RELU, true, true>(c, a, feet, s);   // (bcast_fold: mlp_gemm5.h)
-		if (epi == EPI_MASK && a.vm_bias) return launch_gemm5_t<EPI_MASK, true, true>(c, a, feet, s);
-		if (epi == EPI_BIAS_RELU) return launch_gemm5_t<EPI_BIAS_RELU, true>(c, a, feet, s);
-		if (epi == EPI_MASK) return launch_gemm5_t<EPI_MASK, true>(c, a, feet, s);
-		set_error("launch_gemm5: no fp16-stored variant of this epilogue");
-		return FIND_EINVAL;
-	}
-	if (epi == EPI_BIAS_RELU) return launch_gemm5_t<EPI_BIAS_RELU>(c, a, feet, s);
-	if (epi == EPI_MASK) return launch_gemm5_t<EPI_MASK>(c, a, feet, s);
-	return launch_gemm5_t<EPI_NONE>(c, a, feet, s);
-}
-
-template <int EPI>
-static int launch_gemm7_t(find_ctx* c, Gemm2Args a, int64_t feet, hipStream_t s) {
-	int lds = 0;
-	const int rc = prepare_kernel(c, K_GEMM7_RELU + (EPI == EPI_BIAS_RELU ? 0 : EPI == EPI_MASK ? 1 : 2), &gemm7_kernel<EPI>, GEMM7_LDS, &lds);
-	if (rc != FIND_OK) return rc;
-	a.tiles_per_foot = (int)cdiv(a.V, 32);
-	a.ntiles = (int)(a.tiles_per_foot * feet);
-	const int grid = std::max(16, (c->num_cus / 16) * 16);   // the two column halves of a row range sit 8 blocks apart (same XCD)
-	hipLaunchKernelGGL((gemm7_kernel<EPI>), dim3(grid), dim3(GEMM7_NW * 64), lds, s, a);
-	return FIND_OK;
-}
-
-template <int EPI>
-static int launch_gemm7_virt(find_ctx* c, Gemm2Args a, int64_t feet, hipStream_t s) {   // (bcast_fold: mlp_gemm7.h VIRT)
-	int lds = 0;
-	FIND_TRY(prepare_kernel(c, EPI == EPI_BIAS_RELU ? K_GEMM7_RELU_V : K_GEMM7_MASK_V, &gemm7_kernel<EPI, 0, true>, GEMM7_LDS, &lds));
-	a.tiles_per_foot = (int)cdiv(a.V, 32);
-	a.ntiles = (int)(a.tiles_per_foot * feet);
-	const int grid = std::max(16, (c->num_cus / 16) * 16);
-	hipLaunchKernelGGL((gemm7_kernel<EPI, 0, true>), dim3(grid), dim3(GEMM7_NW * 64), lds, s, a);
-	return FIND_OK;
+	return with_epi(epi, [&](auto E) -> int {
+		constexpr int EPI = decltype(E)::value;
+		const int grid = (int)std::min<int64_t>(c->num_cus, cdiv(ntiles_of(a.V, 32, feet), GEMM5_NW));
+		const int block = GEMM5_NW * 64;
+		if constexpr (EPI != EPI_NONE) {   // fp16-stored A / y / mask (act16): the two epilogues the heads' hidden layers use
+			if (h16 && (EPI == EPI_BIAS_RELU ? a.va_bias : a.vm_bias)) {   // (bcast_fold: mlp_gemm5.h)
+				Gemm2Args v = a;
+				v.tile_major = 1;   // the feet of a tile side by side: the shared product behind the virtual operand is read from HBM once
+				return launch_tiles(c, &gemm5_kernel<EPI, true, true>, TileLaunch{EPI == EPI_BIAS_RELU ? K_GEMM5_RELU_V : K_GEMM5_MASK_V, GEMM5_LDS_VIRT, 32, grid, block}, v, feet, s);
+			}
+			if (h16) return launch_tiles(c, &gemm5_kernel<EPI, true>, TileLaunch{EPI == EPI_BIAS_RELU ? K_GEMM5_RELU_H : K_GEMM5_MASK_H, GEMM5_LDS, 32, grid, block}, a, feet, s);
+		} else if (h16) {
+			set_error("launch_gemm5: no fp16-stored variant of this epilogue");
+			return FIND_EINVAL;
+		}
+		return launch_tiles(c, &gemm5_kernel<EPI>, TileLaunch{K_GEMM5_RELU + epi_slot(EPI), GEMM5_LDS, 32, grid, block}, a, feet, s);
+	});
 }
 
 // workgroup pairs of the folded-foot-sum launch: the usual count, but never so many that a pair's unit range is shorter than a tile's run of
@@ -436,32 +301,26 @@ static int gemm7_fsum_pairs(const find_ctx* c, int64_t V, int64_t feet) {
 	return (feet >= 2 && feet <= 64 && pairs >= 8) ? pairs : 0;
 }
 
-static int launch_gemm7_fsum(find_ctx* c, Gemm2Args a, int64_t feet, hipStream_t s) {   // (footsum_fold: mlp_gemm7.h FSUM)
-	const int pairs = gemm7_fsum_pairs(c, a.V, feet);
-	FIND_REQUIRE(pairs > 0, "launch_gemm7_fsum: shape does not qualify (footsum_fold and the kernel selection disagree)");
-	int lds = 0;
-	FIND_TRY(prepare_kernel(c, K_GEMM7_MASK_VF, &gemm7_kernel<EPI_MASK, 0, true, true>, GEMM7_LDS + 64 * 128 * 4, &lds));
-	a.tiles_per_foot = (int)cdiv(a.V, 32);
-	a.ntiles = (int)(a.tiles_per_foot * feet);
-	a.tile_major = 1;
-	hipLaunchKernelGGL((gemm7_kernel<EPI_MASK, 0, true, true>), dim3(2 * pairs), dim3(GEMM7_NW * 64), lds, s, a);
-	return FIND_OK;
-}
-
 static int launch_gemm7(find_ctx* c, int epi, const Gemm2Args& a, int64_t feet, hipStream_t s) {
-	if (epi == EPI_MASK && a.vm_bias && a.fs_out) return launch_gemm7_fsum(c, a, feet, s);
-	if (epi == EPI_BIAS_RELU && a.va_bias) return launch_gemm7_virt<EPI_BIAS_RELU>(c, a, feet, s);
-	if (epi == EPI_MASK && a.vm_bias) return launch_gemm7_virt<EPI_MASK>(c, a, feet, s);
-	if (epi == EPI_BIAS_RELU) return launch_gemm7_t<EPI_BIAS_RELU>(c, a, feet, s);
-	if (epi == EPI_MASK) return launch_gemm7_t<EPI_MASK>(c, a, feet, s);
-	return launch_gemm7_t<EPI_NONE>(c, a, feet, s);
-}
-
-
-static int launch_gemm3(find_ctx* c, int epi, const Gemm2Args& a, int64_t feet, hipStream_t s) {
-	if (epi == EPI_BIAS_RELU) return launch_gemm3_t<64, EPI_BIAS_RELU>(c, a, feet, s);
-	if (epi == EPI_MASK) return launch_gemm3_t<64, EPI_MASK>(c, a, feet, s);
-	return launch_gemm3_t<64, EPI_NONE>(c, a, feet, s);
+	return with_epi(epi, [&](auto E) -> int {
+		constexpr int EPI = decltype(E)::value;
+		const int grid = std::max(16, (c->num_cus / 16) * 16);   // the two column halves of a row range sit 8 blocks apart (same XCD)
+		const int block = GEMM7_NW * 64;
+		if constexpr (EPI == EPI_MASK) {
+			if (a.vm_bias && a.fs_out) {   // (footsum_fold: mlp_gemm7.h FSUM)
+				const int pairs = gemm7_fsum_pairs(c, a.V, feet);
+				FIND_REQUIRE(pairs > 0, "launch_gemm7: shape does not qualify (footsum_fold and the kernel selection disagree)");
+				Gemm2Args f = a;
+				f.tile_major = 1;
+				return launch_tiles(c, &gemm7_kernel<EPI_MASK, 0, true, true>, TileLaunch{K_GEMM7_MASK_VF, GEMM7_LDS + 64 * 128 * 4, 32, 2 * pairs, block}, f, feet, s);
+			}
+		}
+		if constexpr (EPI != EPI_NONE) {
+			if (EPI == EPI_BIAS_RELU ? a.va_bias : a.vm_bias)   // (bcast_fold: mlp_gemm7.h VIRT)
+				return launch_tiles(c, &gemm7_kernel<EPI, 0, true>, TileLaunch{EPI == EPI_BIAS_RELU ? K_GEMM7_RELU_V : K_GEMM7_MASK_V, GEMM7_LDS, 32, grid, block}, a, feet, s);
+		}
+		return launch_tiles(c, &gemm7_kernel<EPI>, TileLaunch{K_GEMM7_RELU + epi_slot(EPI), GEMM7_LDS, 32, grid, block}, a, feet, s);
+	});
 }
 
 // Kernel choice for one Linear-shaped launch (all of them exact fp32 unless the call runs in the opt-in fp16 mode):
@@ -470,28 +329,21 @@ static int launch_gemm3(find_ctx* c, int epi, const Gemm2Args& a, int64_t feet, 
 //   K = 256, >= gemm4_min_units / 2 32-row units    gemm4<4>        (W half resident in LDS, matrix-pipe-bound)
 //   K = 256, >= gemm4_small units                   gemm4<2>        (column quarters: the shared trunk's V rows)
 //   anything else (two-segment K, tiny launches)    gemm3<64>       (LDS-DMA ring)
-static int launch_gemm(find_ctx* c, int amode, int epi, const GemmArgs& a, int64_t feet, hipStream_t s) {
-	Gemm2Args b;
-	memset(&b, 0, sizeof(b));
-	b.a0 = a.a0; b.a1 = a.a1; b.nseg = a.nbase; b.a_foot_stride = a.a_foot_stride; b.lda = a.lda;
-	b.pos = a.pos; b.pos_foot_stride = a.pos_foot_stride; b.Bm = a.Bm; b.pe = a.pe;
-	b.w0 = a.w0; b.w1 = a.w1; b.ldw = a.ldw; b.nchunk = a.nchunk; b.w_tr = a.w_tr;
-	b.bias = a.bias; b.bias_foot_stride = a.bias_foot_stride; b.mask = a.mask; b.mask_foot_stride = a.mask_foot_stride;
-	b.y = a.y; b.y_foot_stride = a.y_foot_stride; b.ldy = a.ldy; b.V = a.V; b.ablate = c->ablate;
-	b.va_bias = a.va_bias; b.va_bias_stride = a.va_bias_stride; b.vm_bias = a.vm_bias; b.vm_bias_stride = a.vm_bias_stride;
-	b.fs_out = a.fs_out; b.fs_slot_stride = a.fs_slot_stride; b.cs_out = a.cs_out;
-	if (amode == AMODE_PE) return launch_gemm2_pe(c, b, feet, s);
+// h16 (host side only): a0, y and mask are fp16-STORED tensors (act16: gemm5_kernel<EPI, true>)
+static int launch_gemm(find_ctx* c, int amode, int epi, Gemm2Args a, int64_t feet, hipStream_t s, bool h16 = false) {
+	a.ablate = c->ablate;
+	if (amode == AMODE_PE) return launch_gemm2_pe(c, a, feet, s);
 	const int64_t units = cdiv(a.V, 32) * feet;
-	const bool k256 = b.nseg == 1 && b.nchunk == 8;
+	const bool k256 = a.nseg == 1 && a.nchunk == 8;
 	// (gemm5 keeps the whole W per workgroup, so 216 units occupy 27 CUs: 22 us against 13 us for gemm4 on column quarters)
-	if (c->f16 && k256 && units >= c->gemm5_min_units) return launch_gemm5(c, epi, b, feet, s, a.h16 != 0);
-	FIND_REQUIRE(!a.h16, "launch_gemm: an fp16-stored layer reached a kernel that reads fp32 (act16 and the kernel selection disagree)");
-	if (c->x3 && k256 && units >= c->gemm6_min_units) return launch_gemm7(c, epi, b, feet, s);
+	if (c->f16 && k256 && units >= c->gemm5_min_units) return launch_gemm5(c, epi, a, feet, s, h16);
+	FIND_REQUIRE(!h16, "launch_gemm: an fp16-stored layer reached a kernel that reads fp32 (act16 and the kernel selection disagree)");
+	if (c->x3 && k256 && units >= c->gemm6_min_units) return launch_gemm7(c, epi, a, feet, s);
 	FIND_REQUIRE(!a.va_bias && !a.vm_bias && !a.fs_out, "launch_gemm: a virtual operand reached a kernel that cannot form it (bcast_fold / footsum_fold and the kernel selection disagree)");
 	FIND_REQUIRE(!a.w_tr, "launch_gemm: an untransposed weight reached a kernel that cannot read it (gemm7_direct and the kernel selection disagree)");
-	if (k256 && units * 2 >= c->gemm4_min_units) return launch_gemm4<4>(c, epi, b, feet, s);
-	if (k256 && c->gemm4_small && units >= c->gemm4_small) return launch_gemm4<2>(c, epi, b, feet, s);
-	return launch_gemm3(c, epi, b, feet, s);
+	if (k256 && units * 2 >= c->gemm4_min_units) return launch_gemm4<4>(c, epi, a, feet, s);
+	if (k256 && c->gemm4_small && units >= c->gemm4_small) return launch_gemm4<2>(c, epi, a, feet, s);
+	return launch_gemm3(c, epi, a, feet, s);
 }
 
 // a K = 256, one-segment launch of this many rows per foot goes to gemm7 (launch_gemm's rule): its dX form then reads the model's weight
@@ -594,33 +446,21 @@ static bool use_fused(const find_ctx* c, int64_t V, int64_t feet) {
 	return c->fused_max_units > 0 && units <= c->fused_max_units;
 }
 
-static GemmArgs gemm_args_zero() {
-	GemmArgs a;
+static Gemm2Args gemm_args() {
+	Gemm2Args a;
 	memset(&a, 0, sizeof(a));
-	a.nbase = 1;
-	a.nseg_per_base = 1;
+	a.nseg = 1;
 	return a;
 }
 
-// Linear + ReLU forward:  y = relu(x @ w^T + bias[foot])
-static int linear_fwd(find_ctx* c, const float* x, int64_t x_foot_stride, const float* w, int ldw, const float* bias,
-					  int64_t bias_foot_stride, float* y, int64_t V, int64_t feet, hipStream_t s, bool h16 = false, const float* va_bias = nullptr,
-					  int64_t va_bias_stride = 0) {
-	GemmArgs a = gemm_args_zero();
-	a.h16 = h16;
-	a.va_bias = va_bias; a.va_bias_stride = va_bias_stride;   // (then x is the shared fp32 product and x_foot_stride 0: bcast_fold)
+// Linear + ReLU forward:  y = relu(x @ w^T + bias[foot])  (launch_gemm with EPI_BIAS_RELU)
+static Gemm2Args linear_args(const float* x, int64_t x_foot_stride, const float* w, int ldw, const float* bias, int64_t bias_foot_stride, float* y, int64_t V) {
+	Gemm2Args a = gemm_args();
 	a.a0 = x; a.a_foot_stride = x_foot_stride; a.lda = W;
 	a.w0 = w; a.ldw = ldw; a.nchunk = W / KC;
 	a.bias = bias; a.bias_foot_stride = bias_foot_stride;
 	a.y = y; a.y_foot_stride = V * W; a.ldy = W; a.V = (int)V;
-	return launch_gemm(c, AMODE_MAT, EPI_BIAS_RELU, a, feet, s);
-}
-
-static void split_policy(int64_t n_feet, int64_t V, int* spf, int* cps, int64_t target = 128) {
-	const int64_t cpf = cdiv(V, 32);
-	int64_t s0 = std::max<int64_t>(1, std::min<int64_t>(cpf, cdiv(target, n_feet)));
-	*cps = (int)cdiv(cpf, s0);
-	*spf = (int)cdiv(cpf, *cps);
+	return a;
 }
 
 // act16: the opt-in fp16 mode STORES the heads' hidden activations (w.D / w.C) and their gradients (b.dzD / b.dzC) as fp16 when every
@@ -654,11 +494,73 @@ static int noted_act16(const find_ctx* c, const void* ws, bool by_rule, bool fol
 static bool call_f16(const find_ctx* c, const find_mlp_params* p) { return p->precision == 2 || (p->precision == 0 && c->mlp_f16 == 1); }
 static bool call_x3(const find_ctx* c, const find_mlp_params* p) { return p->precision == 3 || (p->precision == 0 && c->mlp_f16 == 2); }
 
-static int mlp_fwd_body(find_ctx* c, Fork& fk, const find_mlp_params* p, const Dims& d, const FwdWs& w, const float* pos, const float* lat_disp,
-						const float* lat_col, float* disp, float* col) {
+// ------------------------------------------------------------------------------------------- forward
+// Everything a call holds once per head: heads[0] the displacement head, heads[1] the colour head (make_heads).  The forward fields are
+// set by every call, the backward ones (from `gout` on) by find_mlp_bwd.
+struct Head {
+	bool colour;
+	int nl;                    // hidden layers; layer nl is the 3-wide output layer
+	const float* const* w;     // the model's weights (p->disp_w / p->col_w) and biases
+	const float* const* b;
+	int ld0;                   // leading dimension of w[0]: 256 + L
+	int L;                     // latent width
+	const float* lat;
+	const float* w0; int ldw0; // the first layer's main block as the forward's kernels read it: the repacked copy, or w[0] itself (chain_direct)
+	float* fb;                 // (n_feet,256) per-foot bias of the first layer (latents folded in)
+	const float* bias0; int64_t bstride0;   // the first layer's bias rows: fb with latents, b[0] without
+	float* const* act;         // saved activations of the hidden layers
+	float* z;
+	float* hp;                 // shared template: (V,256) product of the trunk output with w0 (no bias)
+	float* out;                // forward: the head's output, NULL = not evaluated
+	const float* gout;         // upstream gradient, NULL = nothing read this head
+	float* const* gw; float* const* gb; float* glat;
+	float* const* dz; int cur; // dZ buffers, one per layer, and the one the dX chain has reached
+	float* const* wt;          // transposed weights (layer 0: main block)
+	float* S; float* zs; float* fs1; float* pS;   // (BwdWs: Sd / Sc ...)
+	int side;                  // side stream (and slab set) of the first layer's weight gradient: T1 / T2
+};
+
+static void make_heads(Head* heads, const find_mlp_params* p, const FwdWs& w, const float* lat_disp, const float* lat_col, const BwdWs* b, const find_mlp_grads* g) {
+	memset(heads, 0, 2 * sizeof(Head));
+	Head& d = heads[0];
+	Head& c = heads[1];
+	c.colour = true;
+	d.nl = p->n_disp; c.nl = p->n_col;
+	d.w = p->disp_w; c.w = p->col_w;
+	d.b = p->disp_b; c.b = p->col_b;
+	d.L = p->lat_disp; c.L = p->lat_col;
+	d.lat = lat_disp; c.lat = lat_col;
+	d.w0 = w.wd0; c.w0 = w.wc0;
+	d.fb = w.fbd; c.fb = w.fbc;
+	d.act = w.D; c.act = w.C;
+	d.z = w.zd; c.z = w.zc;
+	d.hp = w.hp; c.hp = w.hp2;   // (the forward may give the colour head w.hp: see there)
+	for (int k = 0; k < 2; ++k) {
+		Head& h = heads[k];
+		h.ld0 = W + h.L;
+		h.ldw0 = W;
+		h.bias0 = h.L > 0 ? h.fb : h.b[0];
+		h.bstride0 = h.L > 0 ? W : 0;
+		h.side = 1 + k;
+	}
+	if (!b) return;
+	d.gw = g->disp_w; c.gw = g->col_w;
+	d.gb = g->disp_b; c.gb = g->col_b;
+	d.glat = g->lat_disp; c.glat = g->lat_col;
+	d.dz = b->dzD; c.dz = b->dzC;
+	d.wt = b->Dt; c.wt = b->Ct;
+	d.S = b->Sd; c.S = b->Sc;
+	d.zs = b->zsD; c.zs = b->zsC;
+	d.fs1 = b->fs1D; c.fs1 = b->fs1C;
+	d.pS = b->pS; c.pS = b->pS2;
+}
+
+static int mlp_fwd_body(Fork& fk, const find_mlp_params* p, const Dims& d, const FwdWs& w, const float* pos, Head* heads) {
+	find_ctx* c = fk.c;
 	hipStream_t s = fk.s;
 	const int64_t V = d.V, n_feet = d.n_feet;
-	const int ld_d0 = W + p->lat_disp, ld_c0 = W + p->lat_col;
+	Head& hd = heads[0];
+	Head& hc = heads[1];
 	const bool a16 = use_act16(c, c->f16, d.shared, n_feet, V);
 	const bool fold = use_fold(c, a16, d.shared, n_feet, V, p);
 	note_act16(c, w.fbd, a16, fold);   // (every forward leaves its note, keyed by a buffer every workspace has: the backward follows it)
@@ -666,42 +568,41 @@ static int mlp_fwd_body(find_ctx* c, Fork& fk, const find_mlp_params* p, const D
 	// 1. repack: layer-0 weight into padded PE order; main blocks of the two head input layers.  Not for a bf16x3 chain that carries the
 	// whole call (or everything up to the heads' broadcast first layers): its weight split reads the model's tensors directly (round 6: this
 	// launch sat in front of both MLP passes of a training step, 8 - 20 us each on the critical path)
-	const bool fused_early = use_fused(c, V, d.feet_t) && p->pe_size > 0;
-	const bool direct = fused_early && chain_direct(c);
+	const bool fused = use_fused(c, V, d.feet_t) && p->pe_size > 0;
+	const bool direct = fused && chain_direct(c);
 	if (!direct) {
 		RepackArgs ra;
 		memset(&ra, 0, sizeof(ra));
 		ra.njobs = 3;
 		ra.job[0] = RepackJob{p->trunk_w[0], w.w0p, W, KP0, p->in_dim + 2 * p->pe_size, 0, KP0, 2, p->pe_size, p->in_dim};
-		ra.job[1] = RepackJob{p->disp_w[0], w.wd0, W, W, ld_d0, 0, W, 0, 0, 0};
-		ra.job[2] = RepackJob{p->col_w[0], w.wc0, W, W, ld_c0, 0, W, 0, 0, 0};
+		ra.job[1] = RepackJob{hd.w[0], w.wd0, W, W, hd.ld0, 0, W, 0, 0, 0};
+		ra.job[2] = RepackJob{hc.w[0], w.wc0, W, W, hc.ld0, 0, W, 0, 0, 0};
 		hipLaunchKernelGGL(repack_kernel, dim3(96, ra.njobs), dim3(256), 0, s, ra);
 		FIND_LAUNCH_CHECK("repack_kernel");
+	} else {
+		for (int k = 0; k < 2; ++k) { heads[k].w0 = heads[k].w[0]; heads[k].ldw0 = heads[k].ld0; }
 	}
 	// 2. per-foot latent bias (model.py:428-437 as a bias)
-	const float* bias_d0 = p->disp_b[0];
-	const float* bias_c0 = p->col_b[0];
-	int64_t bstride_d = 0, bstride_c = 0;
 	// (only for the heads this call evaluates: the template pass of a 3-D-loss step leaves the colour head out, the texture pass the other one)
-	if (p->lat_disp > 0 && disp != nullptr) {
-		hipLaunchKernelGGL(latent_bias_kernel, dim3(W / 4, (unsigned)n_feet), dim3(256), 0, s, p->disp_w[0], ld_d0, p->disp_b[0], lat_disp, p->lat_disp, w.fbd);
-		bias_d0 = w.fbd; bstride_d = W;
-	}
-	if (p->lat_col > 0 && col != nullptr) {
-		hipLaunchKernelGGL(latent_bias_kernel, dim3(W / 4, (unsigned)n_feet), dim3(256), 0, s, p->col_w[0], ld_c0, p->col_b[0], lat_col, p->lat_col, w.fbc);
-		bias_c0 = w.fbc; bstride_c = W;
+	for (int k = 0; k < 2; ++k) {
+		const Head& h = heads[k];
+		if (h.L > 0 && h.out != nullptr)
+			hipLaunchKernelGGL(latent_bias_kernel, dim3(W / 4, (unsigned)n_feet), dim3(256), 0, s, h.w[0], h.ld0, h.b[0], h.lat, h.L, h.fb);
 	}
 	FIND_LAUNCH_CHECK("latent_bias_kernel");
 
+	// The heads are independent after the trunk.  With both active, the colour head runs on a side stream: its bandwidth-bound
+	// pieces (the bias + ReLU broadcast, the 3-wide output layer: no LDS, so they can share CUs with the W-resident GEMMs) then
+	// overlap the other head's matrix-pipe-bound layers.  Forked from and joined back into the caller's stream (Fork::join).
+	const bool forked = hd.out && hc.out && fk.on;
+	// (bcast_fold: the products stay until the backward -- the colour head's is ALWAYS hp2, the other head's hp)
+	if (!(fold || forked || (fused && hd.out))) hc.hp = w.hp;
+
 	// 3 (+ 4, 5 for small calls). trunk (model.py:421-426); layer 0 generates the Fourier features on the fly
-	const bool fused = fused_early;
 	const bool fused_heads = fused && !(d.shared && n_feet > 1);   // per-foot rows: the heads are as small as the trunk
 	if (fused) {
 		Chain ch;
 		ch.a.pos = pos; ch.a.pos_foot_stride = V * 3; ch.a.Bm = p->B; ch.a.pe = p->pe_size; ch.in_dim = p->in_dim;
-		const float* const wd0 = direct ? p->disp_w[0] : w.wd0;
-		const float* const wc0 = direct ? p->col_w[0] : w.wc0;
-		const int ldd0 = direct ? ld_d0 : W, ldc0 = direct ? ld_c0 : W;
 		{
 			// even chunk counts (the padding columns of w0p are zeros; wmode 2 reads them as zeros)
 			FusedStep& s0 = direct ? ch.gemm(p->trunk_w[0], p->in_dim + 2 * p->pe_size, (d.nchunk0 + 1) & ~1) : ch.gemm(w.w0p, KP0, (d.nchunk0 + 1) & ~1);
@@ -715,35 +616,34 @@ static int mlp_fwd_body(find_ctx* c, Fork& fk, const find_mlp_params* p, const D
 		const float* hlast = w.H[p->n_trunk - 1];
 		if (!fused_heads) {
 			// shared template: the first layer of each head is H W0^T on the V template rows (bias + ReLU are broadcast per foot below)
-			if (disp) { FusedStep& st = ch.gemm(wd0, ldd0, W / KC); st.dst = w.hp; }
-			if (col) { FusedStep& st = ch.gemm(wc0, ldc0, W / KC); st.dst = (disp || fold) ? w.hp2 : w.hp; }
+			for (int k = 0; k < 2; ++k)
+				if (heads[k].out) { FusedStep& st = ch.gemm(heads[k].w0, heads[k].ldw0, W / KC); st.dst = heads[k].hp; }
 		} else {
-			auto head = [&](int which, float* const* act, int nl, const float* w0, int ld0, const float* b0, int64_t bstride, const float* const* hw, const float* const* hb,
-							float* z, float* out, bool reload) {
-				FusedStep& f0 = ch.gemm(w0, ld0, W / KC, reload ? hlast : nullptr);
-				f0.relu = 1; f0.bias = b0; f0.bias_foot_stride = (int)bstride; f0.dst = act[0]; f0.to_lds = 1;
-				for (int i = 1; i < nl; ++i) {
-					FusedStep& st = ch.gemm(hw[i], W, W / KC);
-					st.relu = 1; st.bias = hb[i]; st.dst = act[i]; st.to_lds = 1;
+			auto head = [&](const Head& h, bool reload) {
+				FusedStep& f0 = ch.gemm(h.w0, h.ldw0, W / KC, reload ? hlast : nullptr);
+				f0.relu = 1; f0.bias = h.bias0; f0.bias_foot_stride = (int)h.bstride0; f0.dst = h.act[0]; f0.to_lds = 1;
+				for (int i = 1; i < h.nl; ++i) {
+					FusedStep& st = ch.gemm(h.w[i], W, W / KC);
+					st.relu = 1; st.bias = h.b[i]; st.dst = h.act[i]; st.to_lds = 1;
 				}
 				FusedStep& o = ch.add();
-				o.kind = FS_OUT; o.w = hw[nl]; o.bias = hb[nl]; o.dst = out; o.dst2 = z; o.head = (unsigned char)which;
-				o.aux = which ? p->avg_col : nullptr;
+				o.kind = FS_OUT; o.w = h.w[h.nl]; o.bias = h.b[h.nl]; o.dst = h.out; o.dst2 = h.z; o.head = (unsigned char)h.colour;
+				o.aux = h.colour ? p->avg_col : nullptr;
 			};
-			if (disp) head(0, w.D, p->n_disp, wd0, ldd0, bias_d0, bstride_d, p->disp_w, p->disp_b, w.zd, disp, false);
-			if (col) head(1, w.C, p->n_col, wc0, ldc0, bias_c0, bstride_c, p->col_w, p->col_b, w.zc, col, disp != nullptr);
+			if (hd.out) head(hd, false);
+			if (hc.out) head(hc, hd.out != nullptr);
 		}
 		FIND_TRY(launch_chain(c, ch, V, d.feet_t, s, w.w6, chain_w6_bytes(p)));
 		if (fused_heads) return FIND_OK;
 	} else {
-		GemmArgs a = gemm_args_zero();
+		Gemm2Args a = gemm_args();
 		a.pos = pos; a.pos_foot_stride = V * 3; a.Bm = p->B; a.pe = p->pe_size;
 		a.w0 = w.w0p; a.ldw = KP0; a.nchunk = d.nchunk0;
 		a.bias = p->trunk_b[0]; a.bias_foot_stride = 0;
 		a.y = w.H[0]; a.y_foot_stride = V * W; a.ldy = W; a.V = (int)V;
 		FIND_TRY(launch_gemm(c, AMODE_PE, EPI_BIAS_RELU, a, d.feet_t, s));
 		for (int i = 1; i < p->n_trunk; ++i)
-			FIND_TRY(linear_fwd(c, w.H[i - 1], V * W, p->trunk_w[i], W, p->trunk_b[i], 0, w.H[i], V, d.feet_t, s));
+			FIND_TRY(launch_gemm(c, AMODE_MAT, EPI_BIAS_RELU, linear_args(w.H[i - 1], V * W, p->trunk_w[i], W, p->trunk_b[i], 0, w.H[i], V), d.feet_t, s));
 		FIND_LAUNCH_CHECK("trunk gemm");
 	}
 
@@ -753,32 +653,34 @@ static int mlp_fwd_body(find_ctx* c, Fork& fk, const find_mlp_params* p, const D
 	// first layer of a head.  Shared template: every foot multiplies the SAME trunk rows, so  H W^T  is formed once on V rows
 	// and each foot only adds its (latent-folded) bias and applies the ReLU -- a bandwidth-bound broadcast instead of a GEMM
 	// over n_feet * V rows.  (The backward uses the same fact: footsum_kernel.)
-	auto head_first = [&](const float* w0, const float* bias, int64_t bstride, float* out, float* hp, hipStream_t st) -> int {
-		if (hp) {
+	auto head_first = [&](const Head& h, hipStream_t st) -> int {
+		if (h.hp) {
 			if (!fused) {   // (the fused trunk launch has already formed the product)
-				GemmArgs a = gemm_args_zero();
+				Gemm2Args a = gemm_args();
 				a.a0 = hl; a.a_foot_stride = 0; a.lda = W;
-				a.w0 = w0; a.ldw = W; a.nchunk = W / KC;
-				a.y = hp; a.y_foot_stride = V * W; a.ldy = W; a.V = (int)V;
+				a.w0 = h.w0; a.ldw = W; a.nchunk = W / KC;
+				a.y = h.hp; a.y_foot_stride = V * W; a.ldy = W; a.V = (int)V;
 				FIND_TRY(launch_gemm(c, AMODE_MAT, EPI_NONE, a, 1, st));
 			}
 			if (fold) return FIND_OK;   // (the second layer reads hp and the bias rows itself)
-			hipLaunchKernelGGL(bias_relu_bcast_kernel, dim3((unsigned)cdiv(V * (W / 4), 256), (unsigned)cdiv(n_feet, BCAST_FEET)), dim3(256), 0, st, hp, bias,
-							   bstride, (int)n_feet, V, out, a16 ? 1 : 0);
+			hipLaunchKernelGGL(bias_relu_bcast_kernel, dim3((unsigned)cdiv(V * (W / 4), 256), (unsigned)cdiv(n_feet, BCAST_FEET)), dim3(256), 0, st, h.hp, h.bias0,
+							   h.bstride0, (int)n_feet, V, h.act[0], a16 ? 1 : 0);
 			return FIND_OK;
 		}
 		FIND_REQUIRE(!a16, "find_mlp_fwd: act16 without a shared template");
-		return linear_fwd(c, hl, hl_stride, w0, W, bias, bstride, out, V, n_feet, st);
+		return launch_gemm(c, AMODE_MAT, EPI_BIAS_RELU, linear_args(hl, hl_stride, h.w0, W, h.bias0, h.bstride0, h.act[0], V), n_feet, st);
 	};
 	// 5. final 256->3 layers + tanh scalings (model.py:444-449), one launch per head
 	auto head_out = [&](int head, hipStream_t st) {
 		HeadOutArgs h;
 		memset(&h, 0, sizeof(h));
-		h.x[0] = w.D[p->n_disp - 1]; h.x[1] = w.C[p->n_col - 1];
-		h.w[0] = p->disp_w[p->n_disp]; h.w[1] = p->col_w[p->n_col];
-		h.b[0] = p->disp_b[p->n_disp]; h.b[1] = p->col_b[p->n_col];
-		h.z[0] = w.zd; h.z[1] = w.zc;
-		h.out[0] = disp; h.out[1] = col;
+		for (int k = 0; k < 2; ++k) {
+			h.x[k] = heads[k].act[heads[k].nl - 1];
+			h.w[k] = heads[k].w[heads[k].nl];
+			h.b[k] = heads[k].b[heads[k].nl];
+			h.z[k] = heads[k].z;
+			h.out[k] = heads[k].out;
+		}
 		h.avg_col = p->avg_col;
 		h.rows = d.rows_h;
 		h.head0 = head;
@@ -787,190 +689,57 @@ static int mlp_fwd_body(find_ctx* c, Fork& fk, const find_mlp_params* p, const D
 		if (a16) hipLaunchKernelGGL(head_out_fwd_h16_kernel, dim3(gx, 1), dim3(256), 0, st, h);   // (fp16-stored activations: on the fp16 matrix pipe)
 		else hipLaunchKernelGGL(head_out_fwd_kernel, dim3(gx, 1), dim3(256), 0, st, h);
 	};
-	// The heads are independent after the trunk.  With both active, the colour head runs on a side stream: its bandwidth-bound
-	// pieces (the bias + ReLU broadcast, the 3-wide output layer: no LDS, so they can share CUs with the W-resident GEMMs) then
-	// overlap the other head's matrix-pipe-bound layers.  Forked from and joined back into the caller's stream (Fork::join).
+	auto head = [&](const Head& h, hipStream_t st) -> int {
+		FIND_TRY(head_first(h, st));
+		for (int i = 1; i < h.nl; ++i) {
+			Gemm2Args a = linear_args(h.act[i - 1], V * W, h.w[i], W, h.b[i], 0, h.act[i], V);
+			if (i == 1 && fold) {   // (x is the shared fp32 product, the operand relu(hp[v] + bias0[foot]): bcast_fold)
+				a.a0 = h.hp; a.a_foot_stride = 0;
+				a.va_bias = h.bias0; a.va_bias_stride = h.bstride0;
+			}
+			FIND_TRY(launch_gemm(c, AMODE_MAT, EPI_BIAS_RELU, a, n_feet, st, a16));
+		}
+		head_out(h.colour, st);
+		return FIND_OK;
+	};
 	hipStream_t sc = s;
-	if (disp && col && fk.on) {
+	if (forked) {
 		fk.fork_to(1);
 		sc = fk.stream(1);
 	}
-	if (disp) {
-		FIND_TRY(head_first(w.wd0, bias_d0, bstride_d, w.D[0], w.hp, s));
-		for (int i = 1; i < p->n_disp; ++i) {
-			if (i == 1 && fold) FIND_TRY(linear_fwd(c, w.hp, 0, p->disp_w[i], W, p->disp_b[i], 0, w.D[i], V, n_feet, s, a16, bias_d0, bstride_d));
-			else FIND_TRY(linear_fwd(c, w.D[i - 1], V * W, p->disp_w[i], W, p->disp_b[i], 0, w.D[i], V, n_feet, s, a16));
-		}
-		head_out(0, s);
-	}
-	if (col) {
-		// (bcast_fold: the products stay until the backward -- the colour head's is ALWAYS hp2, the other head's hp)
-		float* const hpc = (fold || sc != s || (fused && disp)) ? w.hp2 : w.hp;
-		FIND_TRY(head_first(w.wc0, bias_c0, bstride_c, w.C[0], hpc, sc));
-		for (int i = 1; i < p->n_col; ++i) {
-			if (i == 1 && fold) FIND_TRY(linear_fwd(c, hpc, 0, p->col_w[i], W, p->col_b[i], 0, w.C[i], V, n_feet, sc, a16, bias_c0, bstride_c));
-			else FIND_TRY(linear_fwd(c, w.C[i - 1], V * W, p->col_w[i], W, p->col_b[i], 0, w.C[i], V, n_feet, sc, a16));
-		}
-		head_out(1, sc);
-	}
+	if (hd.out) FIND_TRY(head(hd, s));
+	if (hc.out) FIND_TRY(head(hc, sc));
 	FIND_LAUNCH_CHECK("head layers");
 	return FIND_OK;
 }
 
-}  // namespace mlp
-}  // namespace find
-
-using namespace find;
-using namespace find::mlp;
-
-static int check_ctx(const find_ctx* c, const char* who) {
-	FIND_REQUIRE(c != nullptr, "%s: ctx is NULL (find_ctx_create)", who);
-	int dev = -1;
-	if (hipGetDevice(&dev) != hipSuccess || dev != c->device) {
-		set_error("%s: the context belongs to device %d, the calling thread's current device is %d", who, c->device, dev);
-		return FIND_EINVAL;
-	}
-	return FIND_OK;
-}
-
-extern "C" int64_t find_mlp_ws_bytes(const find_mlp_params* p, int64_t pos_batch, int64_t n_feet, int64_t n_pts, int save_for_bwd) {
-	Dims d;
-	if (make_dims(p, pos_batch, n_feet, n_pts, &d) != FIND_OK) return -1;
-	FwdWs w;
-	carve_fwd(p, d, save_for_bwd != 0, nullptr, &w);
-	return w.bytes;
-}
-
-extern "C" int find_mlp_fwd(find_ctx* c, const find_mlp_params* p, const float* pos, int64_t pos_batch, int64_t n_feet, int64_t n_pts,
-							const float* lat_disp, const float* lat_col, float* disp, float* col, void* ws,
-							int64_t ws_bytes, int save_for_bwd, void* stream) {
-	FIND_TRY(check_ctx(c, "find_mlp_fwd"));
-	Dims d;
-	FIND_TRY(make_dims(p, pos_batch, n_feet, n_pts, &d));
-	FIND_TRY(check_weights(p));
-	FIND_REQUIRE(pos && ws, "find_mlp_fwd: pos/ws is NULL");
-	FIND_REQUIRE(disp || col, "find_mlp_fwd: both outputs NULL");
-	// (the latents of a head the call does not evaluate may be NULL: nothing reads them)
-	FIND_REQUIRE(p->lat_disp == 0 ? lat_disp == nullptr : (lat_disp != nullptr || disp == nullptr), "find_mlp_fwd: lat_disp pointer does not match params.lat_disp=%d", p->lat_disp);
-	FIND_REQUIRE(p->lat_col == 0 ? lat_col == nullptr : (lat_col != nullptr || col == nullptr), "find_mlp_fwd: lat_col pointer does not match params.lat_col=%d", p->lat_col);
-	FIND_REQUIRE(p->precision >= 0 && p->precision <= 3, "find_mlp_fwd: params.precision must be 0 (context default), 1 (fp32 MFMA), 2 (fp16) or 3 (bf16x3), got %d", p->precision);
-	FwdWs w;
-	carve_fwd(p, d, save_for_bwd != 0, ws, &w);
-	if (ws_bytes < w.bytes) {
-		set_error("find_mlp_fwd: workspace too small (%lld < %lld)", (long long)ws_bytes, (long long)w.bytes);
-		return FIND_EWORKSPACE;
-	}
-	c->f16 = call_f16(c, p);
-	c->x3 = call_x3(c, p);
-	Fork fk(c, reinterpret_cast<hipStream_t>(stream), c->fwd_streams != 0);
-	const int rc = mlp_fwd_body(c, fk, p, d, w, pos, lat_disp, lat_col, disp, col);
-	const int rj = fk.join();   // on every path: the caller may free `ws` right after an error return
-	return rc != FIND_OK ? rc : rj;
-}
-
-extern "C" int find_linear_relu_fwd(find_ctx* c, const float* x, const float* w, const float* b, int64_t n_feet, int64_t n_pts, float* y, void* stream) {
-	FIND_TRY(check_ctx(c, "find_linear_relu_fwd"));
-	FIND_REQUIRE(x && w && b && y, "find_linear_relu_fwd: NULL argument");
-	FIND_REQUIRE(n_feet >= 1 && n_pts >= 1 && n_feet < (1 << 16), "find_linear_relu_fwd: bad sizes");
-	FIND_REQUIRE(aligned16(w) && aligned16(x), "find_linear_relu_fwd: x and w must be 16-byte aligned");
-	c->f16 = c->mlp_f16 == 1;
-	c->x3 = c->mlp_f16 == 2;
-	FIND_TRY(linear_fwd(c, x, n_pts * W, w, W, b, 0, y, n_pts, n_feet, reinterpret_cast<hipStream_t>(stream)));
-	FIND_LAUNCH_CHECK("find_linear_relu_fwd");
-	return FIND_OK;
-}
-
 // ------------------------------------------------------------------------------------------- backward
-namespace find {
-namespace mlp {
-
-struct BwdWs {
-	float* Tt[FIND_MAX_LAYERS];  // transposed trunk weights (layers >= 1)
-	float* Dt[FIND_MAX_LAYERS];  // transposed disp-head weights (layer 0: main block)
-	float* Ct[FIND_MAX_LAYERS];
-	float* dzD[FIND_MAX_LAYERS];  // one per head layer (as dzT)
-	float* dzC[FIND_MAX_LAYERS];
-	float* dzT[FIND_MAX_LAYERS];  // one per trunk layer: the dX chain never waits for the side stream's readers
-	float* pw;    // dW partial slabs
-	float* pb;    // bias partial slabs
-	float* pw_t[4];  // slab sets: [0] aliases pw / pb (stream q), [1], [2] the trunk's side streams, [3] alternates with [0] on q
-	float* pb_t[4];
-	float* Sd;    // (n_feet,256) per-foot column sums of the disp head's first-layer dZ
-	float* Sc;
-	float* zsD;   // shared template: (V,256) sum over feet of the disp head's first-layer dZ
-	float* zsC;
-	float* fs1D;  // footsum_fold: the second partial sum of gemm7_kernel<.., FSUM> (the first lands in zsD / zsC)
-	float* fs1C;
-	float* pS;    // [nblk_fs][n_feet][256] partial per-foot column sums (disp head)
-	float* pS2;   // same for the colour head: the reduces run on the side stream, so the heads cannot share one
-	int nblk_fs;
-	float* pwo[2];  // final-layer partials
-	float* pbo[2];
-	int nblk_out;
-	int64_t max_split;
-	float* grp_pw;   // small calls: slabs of the grouped weight-gradient launch, [job][slab][256][256], then the bias rows [job][slab][256]
-	int64_t grp_slabs;  // slabs per job
-	int grp_jobs;
-	void* w6;        // fused6_kernel: the dX chain's weights as fragment-ordered bf16 planes
-	int64_t bytes;
+// One weight-gradient job: dW / db of one Linear layer from dz (rows (foot, v)) and its input x (or, for the Fourier layer, the positions).
+struct Wgrad {
+	const float* dz = nullptr;
+	const float* x = nullptr;        // the layer's input; x_foot_stride 0 = rows shared by all feet
+	int64_t x_foot_stride = 0;
+	const float* pos = nullptr;      // Fourier layer: the inputs are regenerated from the positions (x unused)
+	int64_t pos_foot_stride = 0;
+	int nkt = 1;                     // Fourier layer: 256-wide k tiles (Dims::nkt0)
+	int64_t feet = 1, V = 0;
+	float* dw = nullptr;
+	int ld_out = W;
+	int k_valid = W;
+	int pe_map = 0;                  // Fourier layer: columns go back to the model's order
+	float* db = nullptr;
+	float* S = nullptr;              // per-foot column sums of dz (latent gradients)
+	hipStream_t s = nullptr;         // the partial tiles go out on s; the slab reduce follows on s, or -- reduce_side >= 0 -- on that side
+	int s_side = -1;                 // stream of the fork, ordered behind s (= side stream s_side)
+	int reduce_side = -1;
+	bool h16 = false;                // dz and x fp16-stored (act16)
+	const float* vx_bias = nullptr;  // bcast_fold: x is the shared product P, the operand relu(P[v] + vx_bias[foot])
+	int64_t vx_bias_stride = 0;
 };
 
-constexpr int64_t GROUP_MAX_UNITS = 1024;   // largest call (32-row tiles) that may take the fused / grouped small-call path
-constexpr int GROUP_MIN_CPS = 8;            // 16-row chunks per workgroup of a grouped weight gradient, at least
-
-static void carve_bwd(const find_mlp_params* p, const Dims& d, void* scratch, BwdWs* o) {
-	Carver c(scratch);
-	for (int i = 1; i < p->n_trunk; ++i) o->Tt[i] = c.take<float>((int64_t)W * W);
-	for (int i = 0; i < p->n_disp; ++i) o->Dt[i] = c.take<float>((int64_t)W * W);
-	for (int i = 0; i < p->n_col; ++i) o->Ct[i] = c.take<float>((int64_t)W * W);
-	for (int i = 0; i < std::max(p->n_disp, 1); ++i) o->dzD[i] = c.take<float>(d.rows_h * W);
-	for (int i = 0; i < std::max(p->n_col, 1); ++i) o->dzC[i] = c.take<float>(d.rows_h * W);
-	for (int i = 0; i < std::max(p->n_trunk, 1); ++i) o->dzT[i] = c.take<float>(d.rows_t * W);
-	int spf, cps;
-	split_policy(d.n_feet, d.V, &spf, &cps);
-	int64_t ms = d.n_feet * spf;
-	split_policy(1, d.V, &spf, &cps);
-	ms = std::max<int64_t>(ms, spf);
-	o->max_split = ms;
-	// dw2 policy: up to max(#CUs, feet) main slabs + one tail slab per foot, each 256x256
-	const int64_t ms2 = std::max<int64_t>(512, d.n_feet) + d.n_feet + 16;
-	o->pw = c.take<float>(std::max<int64_t>(ms * W * KP0, ms2 * W * W));
-	o->pb = c.take<float>(std::max<int64_t>(ms, ms2) * W);
-	o->pw_t[0] = o->pw; o->pb_t[0] = o->pb;
-	for (int i = 1; i < 4; ++i) {  // trunk layers have matrix inputs (dw2 slabs) except layer 0, which always uses set 0
-		o->pw_t[i] = c.take<float>(ms2 * W * W);
-		o->pb_t[i] = c.take<float>(ms2 * W);
-	}
-	o->Sd = c.take<float>(d.n_feet * W);
-	o->Sc = c.take<float>(d.n_feet * W);
-	o->nblk_fs = (int)cdiv(d.V, FS_ROWS);
-	if (d.shared) {
-		o->zsD = c.take<float>(d.V * W);
-		o->zsC = c.take<float>(d.V * W);
-		o->fs1D = c.take<float>(d.V * W);
-		o->fs1C = c.take<float>(d.V * W);
-	} else {
-		o->zsD = o->zsC = o->fs1D = o->fs1C = nullptr;
-	}
-	// (also without a shared template: the latents-only backward of a frozen network takes its per-foot column sums this way)
-	o->pS = c.take<float>((int64_t)o->nblk_fs * d.n_feet * W);
-	o->pS2 = c.take<float>((int64_t)o->nblk_fs * d.n_feet * W);
-	o->w6 = c.take<char>(chain_w6_bytes(p));
-	o->grp_pw = nullptr; o->grp_slabs = 0; o->grp_jobs = 0;
-	if (cdiv(d.V, 32) * d.feet_t <= GROUP_MAX_UNITS) {
-		// (a shared trunk groups its own layers only: the heads' layers there have n_feet times the rows and keep their own launches)
-		// (round 6: ... and the heads' FIRST layers, whose foot-summed gradient has the trunk's V rows)
-		o->grp_jobs = d.shared ? (p->n_trunk - 1) + 2 : (p->n_trunk - 1) + p->n_disp + p->n_col;
-		o->grp_slabs = std::max<int64_t>(d.feet_t * (cdiv(d.V / 16, GROUP_MIN_CPS) + 1), std::min<int64_t>(d.feet_t * cdiv(d.V / 16, 2), 32));
-		if (o->grp_jobs > 0) o->grp_pw = c.take<float>((int64_t)o->grp_jobs * o->grp_slabs * ((int64_t)W * W + W));
-	}
-	o->nblk_out = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(d.rows_h, 64), 512));
-	for (int i = 0; i < 2; ++i) {
-		o->pwo[i] = c.take<float>((int64_t)o->nblk_out * 3 * W);
-		o->pbo[i] = c.take<float>((int64_t)o->nblk_out * 4);
-	}
-	o->bytes = c.off;
-}
+// partial slabs of one weight-gradient launch: dW tiles and bias rows
+struct Slabs { float* pw; float* pb; };
+static Slabs slabs(const BwdWs& b, int k) { return Slabs{b.pw_t[k], b.pb_t[k]}; }
 
 // (diagnosis) dynamic LDS of the slab reduce: 0, or everything the CU has left beside its 16 KB of static LDS
 static int reduce_lds(find_ctx* c) {
@@ -983,42 +752,46 @@ static int reduce_lds(find_ctx* c) {
 	return dyn;
 }
 
-// dW / db of one Linear layer from dz (rows (foot, v)) and its input x (or, for the Fourier layer, the positions).  The partial
-// tiles go out on stream s; the slab reduce follows on s, or -- reduce_side >= 0 -- on that side stream of the fork, ordered behind s.
-static int weight_grad(find_ctx* c, Fork* fk, const float* dz, const float* x, int64_t x_foot_stride, const float* pos, int64_t pos_foot_stride,
-					   const find_mlp_params* p, int nkt, int64_t feet, int64_t V, const BwdWs& b, float* dw, int ld_out,
-					   int k_valid, int pe_map, float* db, float* S, hipStream_t s, int s_side = -1, int reduce_side = -1, bool h16 = false,
-					   const float* vx_bias = nullptr, int64_t vx_bias_stride = 0) {   // (vx_bias: bcast_fold -- x is the shared product P, the operand relu(P[v] + vx_bias[foot]))
-	FIND_REQUIRE(!vx_bias || (!pos && ((h16 && c->f16) || (!c->f16 && c->x3 && cdiv(V, 32) * feet >= c->gemm6_min_units))),
+static int launch_reduce(find_ctx* c, const ReduceWArgs& r, hipStream_t s) {
+	const unsigned grid = (unsigned)(r.nwblk + (r.pb ? r.n_feet + 1 : 0));
+	if (c->reduce_exclusive == 2) hipLaunchKernelGGL(reduce_w_nolds_kernel, dim3(grid), dim3(1024), 0, s, r);
+	else hipLaunchKernelGGL(reduce_w_kernel, dim3(grid), dim3(1024), reduce_lds(c), s, r);
+	FIND_LAUNCH_CHECK("reduce_w_kernel");
+	return FIND_OK;
+}
+
+static int weight_grad(find_ctx* c, Fork* fk, const find_mlp_params* p, const Wgrad& in, Slabs sl) {
+	const int64_t feet = in.feet, V = in.V;
+	hipStream_t s = in.s;
+	FIND_REQUIRE(!in.vx_bias || (!in.pos && ((in.h16 && c->f16) || (!c->f16 && c->x3 && cdiv(V, 32) * feet >= c->gemm6_min_units))),
 				 "weight_grad: a virtual operand reached a kernel that cannot form it (bcast_fold and the kernel selection disagree)");
-	auto reduce_stream = [&]() -> hipStream_t {
-		if (!fk || !fk->on || reduce_side < 0 || s_side < 0 || reduce_side == s_side) return s;
-		fk->chain(s_side, reduce_side);
-		return fk->stream(reduce_side);
-	};
-	float* pbuf = (db || S) ? b.pb : nullptr;
+	float* pbuf = (in.db || in.S) ? sl.pb : nullptr;
 	const int cus = c->num_cus;
-	if (!pos) {
-		int nmain, spf;
+	int nsplit, spf, Kp = 256;
+	if (!in.pos) {
+		auto dw3_args = [&](int cpf, int cps) {
+			Dw3Args a;
+			memset(&a, 0, sizeof(a));
+			a.dz = in.dz; a.dz_foot_stride = V * W; a.x = in.x; a.x_foot_stride = in.x_foot_stride;
+			a.V = (int)V; a.chunks_per_foot = cpf; a.spf = spf; a.cps = cps; a.pw = sl.pw; a.pb = pbuf;
+			a.xbias = in.vx_bias; a.xbias_stride = in.vx_bias_stride;
+			return a;
+		};
 		if (c->f16) {
 			// opt-in fp16 mode: 64-row chunks, rows past the end of a foot zero-filled by the kernel
 			const int cpf64 = (int)cdiv(V, 64);
 			const int want = (int)std::max<int64_t>(1, std::min<int64_t>(cpf64, cdiv(cus, feet)));
 			const int cps3 = (int)std::max<int64_t>(cdiv(cpf64, want), std::min<int>(4, cpf64));  // at least 256 rows per slab (the small launches are slab-bound)
 			spf = (int)cdiv(cpf64, cps3);
-			nmain = (int)(feet * spf);
+			nsplit = (int)(feet * spf);
 			int lds = 0;
-			if (vx_bias) FIND_TRY(prepare_kernel(c, K_DW3_V, &dw3_h16v_kernel, DW3_LDS, &lds));
-			else if (h16) FIND_TRY(prepare_kernel(c, K_DW3_H, &dw3_h16_kernel, DW3_LDS, &lds));
+			if (in.vx_bias) FIND_TRY(prepare_kernel(c, K_DW3_V, &dw3_h16v_kernel, DW3_LDS, &lds));
+			else if (in.h16) FIND_TRY(prepare_kernel(c, K_DW3_H, &dw3_h16_kernel, DW3_LDS, &lds));
 			else FIND_TRY(prepare_kernel(c, K_DW3, &dw3_kernel, DW3_LDS, &lds));
-			Dw3Args d3;
-			memset(&d3, 0, sizeof(d3));
-			d3.dz = dz; d3.dz_foot_stride = V * W; d3.x = x; d3.x_foot_stride = x_foot_stride;
-			d3.V = (int)V; d3.chunks_per_foot = cpf64; d3.spf = spf; d3.cps = cps3; d3.pw = b.pw; d3.pb = pbuf;
-			d3.xbias = vx_bias; d3.xbias_stride = vx_bias_stride;
-			if (vx_bias) hipLaunchKernelGGL(dw3_h16v_kernel, dim3((unsigned)nmain), dim3(256), lds, s, d3);   // (x formed from the shared product: bcast_fold)
-			else if (h16) hipLaunchKernelGGL(dw3_h16_kernel, dim3((unsigned)nmain), dim3(256), lds, s, d3);   // (dz and x fp16-stored: act16)
-			else hipLaunchKernelGGL(dw3_kernel, dim3((unsigned)nmain), dim3(256), lds, s, d3);
+			const Dw3Args d3 = dw3_args(cpf64, cps3);
+			if (in.vx_bias) hipLaunchKernelGGL(dw3_h16v_kernel, dim3((unsigned)nsplit), dim3(256), lds, s, d3);   // (x formed from the shared product: bcast_fold)
+			else if (in.h16) hipLaunchKernelGGL(dw3_h16_kernel, dim3((unsigned)nsplit), dim3(256), lds, s, d3);   // (dz and x fp16-stored: act16)
+			else hipLaunchKernelGGL(dw3_kernel, dim3((unsigned)nsplit), dim3(256), lds, s, d3);
 			FIND_LAUNCH_CHECK("dw3_kernel");
 		} else if (c->x3 && cdiv(V, 32) * feet >= c->gemm6_min_units) {
 			// bf16x3: 16-row chunks, rows past the end of a foot zero-filled by the kernel; few, long runs (slab traffic)
@@ -1030,17 +803,13 @@ static int weight_grad(find_ctx* c, Fork* fk, const float* dz, const float* x, i
 			const int want = (int)std::max<int64_t>(1, std::min<int64_t>(cpf16, cdiv(wgs6, feet)));
 			const int cps6 = (int)std::max<int64_t>(cdiv(cpf16, want), std::min<int>(c->dw2_min_cps, cpf16));
 			spf = (int)cdiv(cpf16, cps6);
-			nmain = (int)(feet * spf);
+			nsplit = (int)(feet * spf);
 			int lds = 0;
-			if (vx_bias) FIND_TRY(prepare_kernel(c, K_DW6_V, &dw6v_kernel, DW6_LDS, &lds));
+			if (in.vx_bias) FIND_TRY(prepare_kernel(c, K_DW6_V, &dw6v_kernel, DW6_LDS, &lds));
 			else FIND_TRY(prepare_kernel(c, K_DW6, &dw6_kernel, DW6_LDS, &lds));
-			Dw3Args d6;
-			memset(&d6, 0, sizeof(d6));
-			d6.dz = dz; d6.dz_foot_stride = V * W; d6.x = x; d6.x_foot_stride = x_foot_stride;
-			d6.V = (int)V; d6.chunks_per_foot = cpf16; d6.spf = spf; d6.cps = cps6; d6.pw = b.pw; d6.pb = pbuf;
-			d6.xbias = vx_bias; d6.xbias_stride = vx_bias_stride;
-			if (vx_bias) hipLaunchKernelGGL(dw6v_kernel, dim3((unsigned)nmain), dim3(256), lds, s, d6);   // (x formed from the shared product: bcast_fold)
-			else hipLaunchKernelGGL(dw6_kernel, dim3((unsigned)nmain), dim3(256), lds, s, d6);
+			const Dw3Args d6 = dw3_args(cpf16, cps6);
+			if (in.vx_bias) hipLaunchKernelGGL(dw6v_kernel, dim3((unsigned)nsplit), dim3(256), lds, s, d6);   // (x formed from the shared product: bcast_fold)
+			else hipLaunchKernelGGL(dw6_kernel, dim3((unsigned)nsplit), dim3(256), lds, s, d6);
 			FIND_LAUNCH_CHECK("dw6_kernel");
 		} else {
 			// LDS-DMA kernel: every foot's rows cut into spf contiguous runs of 16-row chunks, the <= 15 leftover rows
@@ -1056,60 +825,55 @@ static int weight_grad(find_ctx* c, Fork* fk, const float* dz, const float* x, i
 				cps2 = (int)std::max<int64_t>(cdiv(cpf16, want), std::min<int>(floor_cps, cpf16));
 				spf = (int)cdiv(cpf16, cps2);
 			}
-			nmain = (int)(feet * spf);
+			nsplit = (int)(feet * spf);
 			int lds = 0;
 			if (c->dw_lds_free == 0) FIND_TRY(prepare_kernel(c, K_DW2, &dw2_kernel, DW2_LDS, &lds));
 			Dw2Args d2;
 			memset(&d2, 0, sizeof(d2));
-			d2.dz = dz; d2.dz_foot_stride = V * W; d2.x = x; d2.x_foot_stride = x_foot_stride;
-			d2.chunks_per_foot = cpf16; d2.tail_rows = (int)(V % 16); d2.spf = spf; d2.cps = cps2; d2.pw = b.pw; d2.pb = pbuf;
-			if (c->dw_lds_free == 1) hipLaunchKernelGGL(dw4_kernel, dim3((unsigned)nmain), dim3(512), 0, s, d2);
-			else hipLaunchKernelGGL(dw2_kernel, dim3((unsigned)nmain), dim3(256), lds, s, d2);
+			d2.dz = in.dz; d2.dz_foot_stride = V * W; d2.x = in.x; d2.x_foot_stride = in.x_foot_stride;
+			d2.chunks_per_foot = cpf16; d2.tail_rows = (int)(V % 16); d2.spf = spf; d2.cps = cps2; d2.pw = sl.pw; d2.pb = pbuf;
+			if (c->dw_lds_free == 1) hipLaunchKernelGGL(dw4_kernel, dim3((unsigned)nsplit), dim3(512), 0, s, d2);
+			else hipLaunchKernelGGL(dw2_kernel, dim3((unsigned)nsplit), dim3(256), lds, s, d2);
 			FIND_LAUNCH_CHECK("dw2_kernel");
 		}
-		ReduceWArgs r;
-		memset(&r, 0, sizeof(r));
-		r.pw = b.pw; r.nsplit = nmain; r.Kp = 256; r.out = dw; r.ld_out = ld_out; r.K_valid = k_valid;
-		r.pb = pbuf; r.n_feet = (int)feet; r.spf = spf; r.db = db; r.S = S;
-		r.nwblk = 256 * 256 / 4 / 64;
-		if (c->reduce_exclusive == 2) hipLaunchKernelGGL(reduce_w_nolds_kernel, dim3((unsigned)(r.nwblk + (pbuf ? (int)feet + 1 : 0))), dim3(1024), 0, reduce_stream(), r);
-		else hipLaunchKernelGGL(reduce_w_kernel, dim3((unsigned)(r.nwblk + (pbuf ? (int)feet + 1 : 0))), dim3(1024), reduce_lds(c), reduce_stream(), r);
-		FIND_LAUNCH_CHECK("reduce_w_kernel");
-		return FIND_OK;
+	} else {
+		// Fourier layer: the inputs are regenerated from the positions.  dwpe_kernel (mlp_dwpe.h; pe >= 32): one k-tile of workgroups per 128
+		// frequencies, slabs of 2 pe + 32 columns; dw_kernel<AMODE_PE> (round 1, LDS-staged; pe < 32): nkt k-tiles, slabs of 256 nkt columns.
+		// Either way the launch stays within one round of workgroups over the chip (at most 256).
+		const bool lds_free = p->pe_size >= 32;
+		const int nkt_launch = lds_free ? (int)cdiv(p->pe_size, 128) : in.nkt;
+		int cps;
+		split_policy(feet, V, &spf, &cps, std::min<int64_t>(128, std::max<int64_t>(16, std::min(256, cus) / nkt_launch)));
+		DwArgs a;
+		memset(&a, 0, sizeof(a));
+		a.dz = in.dz; a.dz_foot_stride = V * W;
+		a.x = in.x; a.x_foot_stride = in.x_foot_stride; a.ldx = W;
+		a.pos = in.pos; a.pos_foot_stride = in.pos_foot_stride; a.Bm = p->B; a.pe = p->pe_size;
+		a.V = (int)V; a.spf = spf; a.cps = cps; a.Kp = lds_free ? 2 * p->pe_size + 32 : in.nkt * 256;
+		a.pw = sl.pw; a.pb = pbuf;
+		a.all_blocks = (c->ablate & 32) ? 1 : 0;
+		nsplit = (int)(feet * spf);
+		Kp = a.Kp;
+		if (lds_free && (c->x3 || c->f16)) {   // bf16x3 calls (and the opt-in fp16 mode, whose Fourier layer keeps fp32-class arithmetic): the sin / cos columns on the bf16 matrix pipe, the x, y, z columns and the bias sums beside them
+			hipLaunchKernelGGL(dwpe6_kernel, dim3((unsigned)nkt_launch, (unsigned)nsplit), dim3(512), 0, s, a);
+			hipLaunchKernelGGL(dwxyz_kernel, dim3((unsigned)nsplit), dim3(1024), 0, s, a);
+		}
+		else if (lds_free) hipLaunchKernelGGL(dwpe_kernel, dim3((unsigned)nkt_launch, (unsigned)nsplit), dim3(512), 0, s, a);
+		else hipLaunchKernelGGL((dw_kernel<AMODE_PE>), dim3((unsigned)in.nkt, (unsigned)nsplit), dim3(512), 0, s, a);
+		FIND_LAUNCH_CHECK("dw_kernel");
 	}
-	// Fourier layer: the inputs are regenerated from the positions.  dwpe_kernel (mlp_dwpe.h; pe >= 32): one k-tile of workgroups per 128
-	// frequencies, slabs of 2 pe + 32 columns; dw_kernel<AMODE_PE> (round 1, LDS-staged; pe < 32): nkt k-tiles, slabs of 256 nkt columns.
-	// Either way the launch stays within one round of workgroups over the chip (at most 256).
-	const bool lds_free = p->pe_size >= 32;
-	const int nkt_launch = lds_free ? (int)cdiv(p->pe_size, 128) : nkt;
-	int spf, cps;
-	split_policy(feet, V, &spf, &cps, std::min<int64_t>(128, std::max<int64_t>(16, std::min(256, cus) / nkt_launch)));
-	DwArgs a;
-	memset(&a, 0, sizeof(a));
-	a.dz = dz; a.dz_foot_stride = V * W;
-	a.x = x; a.x_foot_stride = x_foot_stride; a.ldx = W;
-	a.pos = pos; a.pos_foot_stride = pos_foot_stride; a.Bm = p->B; a.pe = p->pe_size;
-	a.V = (int)V; a.spf = spf; a.cps = cps; a.Kp = lds_free ? 2 * p->pe_size + 32 : nkt * 256;
-	a.pw = b.pw; a.pb = pbuf;
-	a.all_blocks = (c->ablate & 32) ? 1 : 0;
-	const int nsplit = (int)(feet * spf);
-	if (lds_free && (c->x3 || c->f16)) {   // bf16x3 calls (and the opt-in fp16 mode, whose Fourier layer keeps fp32-class arithmetic): the sin / cos columns on the bf16 matrix pipe, the x, y, z columns and the bias sums beside them
-		hipLaunchKernelGGL(dwpe6_kernel, dim3((unsigned)nkt_launch, (unsigned)nsplit), dim3(512), 0, s, a);
-		hipLaunchKernelGGL(dwxyz_kernel, dim3((unsigned)nsplit), dim3(1024), 0, s, a);
-	}
-	else if (lds_free) hipLaunchKernelGGL(dwpe_kernel, dim3((unsigned)nkt_launch, (unsigned)nsplit), dim3(512), 0, s, a);
-	else hipLaunchKernelGGL((dw_kernel<AMODE_PE>), dim3((unsigned)nkt, (unsigned)nsplit), dim3(512), 0, s, a);
-	FIND_LAUNCH_CHECK("dw_kernel");
 	ReduceWArgs r;
 	memset(&r, 0, sizeof(r));
-	r.pw = b.pw; r.nsplit = nsplit; r.Kp = a.Kp; r.out = dw; r.ld_out = ld_out; r.K_valid = k_valid;
-	r.pe_map = pe_map; r.pe = p->pe_size; r.in_dim = p->in_dim;
-	r.pb = a.pb; r.n_feet = (int)feet; r.spf = spf; r.db = db; r.S = S;
-	r.nwblk = 256 * a.Kp / 4 / 64;
-	if (c->reduce_exclusive == 2) hipLaunchKernelGGL(reduce_w_nolds_kernel, dim3((unsigned)(r.nwblk + (a.pb ? (int)feet + 1 : 0))), dim3(1024), 0, reduce_stream(), r);
-	else hipLaunchKernelGGL(reduce_w_kernel, dim3((unsigned)(r.nwblk + (a.pb ? (int)feet + 1 : 0))), dim3(1024), reduce_lds(c), reduce_stream(), r);
-	FIND_LAUNCH_CHECK("reduce_w_kernel");
-	return FIND_OK;
+	r.pw = sl.pw; r.nsplit = nsplit; r.Kp = Kp; r.out = in.dw; r.ld_out = in.ld_out; r.K_valid = in.k_valid;
+	if (in.pos) { r.pe_map = in.pe_map; r.pe = p->pe_size; r.in_dim = p->in_dim; }
+	r.pb = pbuf; r.n_feet = (int)feet; r.spf = spf; r.db = in.db; r.S = in.S;
+	r.nwblk = 256 * Kp / 4 / 64;
+	hipStream_t rs = s;
+	if (fk && fk->on && in.reduce_side >= 0 && in.s_side >= 0 && in.reduce_side != in.s_side) {
+		fk->chain(in.s_side, in.reduce_side);
+		rs = fk->stream(in.reduce_side);
+	}
+	return launch_reduce(c, r, rs);
 }
 
 // Grouped weight gradients of a small call: every 256 x 256 layer's dW / db (and per-foot column sums) in ONE dw2 launch + ONE slab reduce.
@@ -1143,9 +907,9 @@ static void group_geometry(const find_ctx* c, int cpf16, int64_t feet, int jobs,
 	}
 }
 
-static int wgrad_group_add(find_ctx* c, WgradGroup& G, const BwdWs& b, const float* dz, const float* x, int64_t x_foot_stride, int64_t feet, int64_t V,
-						   float* dw, int ld_out, float* db, float* S) {
+static int wgrad_group_add(find_ctx* c, WgradGroup& G, const BwdWs& b, const Wgrad& in) {
 	FIND_REQUIRE(G.n < b.grp_jobs && G.n < DW2_MAX_JOBS && G.n < DW6_MAX_JOBS, "find_mlp_bwd: too many grouped weight gradients");
+	const int64_t feet = in.feet, V = in.V;
 	// bf16x3 calls: dw6_group_kernel (16-row chunks, rows past a foot's end zero-filled by the loads: ceil); the others dw4_group (tail rows folded)
 	G.x3 = c->x3 && c->dw_lds_free == 1;
 	const int cpf16 = G.x3 ? (int)cdiv(V, 16) : (int)(V / 16);
@@ -1156,14 +920,14 @@ static int wgrad_group_add(find_ctx* c, WgradGroup& G, const BwdWs& b, const flo
 	float* pw = b.grp_pw + (int64_t)G.n * b.grp_slabs * W * W;
 	float* pb = b.grp_pw + (int64_t)b.grp_jobs * b.grp_slabs * W * W + (int64_t)G.n * b.grp_slabs * W;
 	Dw2Args& d2 = G.d.job[G.n];
-	d2.dz = dz; d2.dz_foot_stride = V * W; d2.x = x; d2.x_foot_stride = x_foot_stride;
-	d2.chunks_per_foot = cpf16; d2.tail_rows = (int)(V % 16); d2.spf = spf; d2.cps = cps2; d2.pw = pw; d2.pb = (db || S) ? pb : nullptr;
+	d2.dz = in.dz; d2.dz_foot_stride = V * W; d2.x = in.x; d2.x_foot_stride = in.x_foot_stride;
+	d2.chunks_per_foot = cpf16; d2.tail_rows = (int)(V % 16); d2.spf = spf; d2.cps = cps2; d2.pw = pw; d2.pb = (in.db || in.S) ? pb : nullptr;
 	Dw3Args& d6 = G.d6.job[G.n];
-	d6.dz = dz; d6.dz_foot_stride = V * W; d6.x = x; d6.x_foot_stride = x_foot_stride;
+	d6.dz = in.dz; d6.dz_foot_stride = V * W; d6.x = in.x; d6.x_foot_stride = in.x_foot_stride;
 	d6.V = (int)V; d6.chunks_per_foot = cpf16; d6.spf = spf; d6.cps = cps2; d6.pw = pw; d6.pb = d2.pb;
 	ReduceWArgs& r = G.r.job[G.n];
-	r.pw = pw; r.nsplit = nmain; r.Kp = 256; r.out = dw; r.ld_out = ld_out; r.K_valid = W;
-	r.pb = d2.pb; r.n_feet = (int)feet; r.spf = spf; r.db = db; r.S = S;
+	r.pw = pw; r.nsplit = nmain; r.Kp = 256; r.out = in.dw; r.ld_out = in.ld_out; r.K_valid = W;
+	r.pb = d2.pb; r.n_feet = (int)feet; r.spf = spf; r.db = in.db; r.S = in.S;
 	r.nwblk = 256 * 256 / 4 / 64;
 	G.nmain = nmain; G.feet = feet;   // (every job of a group has the same geometry)
 	G.n += 1;
@@ -1189,28 +953,15 @@ static int wgrad_group_launch(find_ctx* c, WgradGroup& G, hipStream_t s) {
 	return FIND_OK;
 }
 
-// masked dX:  y = (dz @ W) * (mask > 0), with W given pre-transposed
-// (vm_bias: bcast_fold -- mask is the shared fp32 product P and the layer's output was relu(P[v] + vm_bias[foot]))
-static int linear_bwd_dx(find_ctx* c, const float* dz, const float* wt, int ldw, int w_tr, const float* mask, float* y, int64_t V, int64_t feet, hipStream_t s, bool h16 = false,
-						 const float* vm_bias = nullptr, int64_t vm_bias_stride = 0, float* fs_out = nullptr, int64_t fs_slot_stride = 0, float* cs_out = nullptr) {
-	GemmArgs a = gemm_args_zero();
-	a.h16 = h16;
-	a.fs_out = fs_out; a.fs_slot_stride = fs_slot_stride; a.cs_out = cs_out;   // (footsum_fold: y is then not written)
-	a.a0 = dz; a.a_foot_stride = V * W; a.lda = W;
-	a.w0 = wt; a.ldw = ldw; a.w_tr = w_tr; a.nchunk = W / KC;
-	a.mask = mask; a.mask_foot_stride = vm_bias ? 0 : V * W;
-	a.vm_bias = vm_bias; a.vm_bias_stride = vm_bias_stride;
-	a.y = y; a.y_foot_stride = V * W; a.ldy = W; a.V = (int)V;
-	return launch_gemm(c, AMODE_MAT, EPI_MASK, a, feet, s);
-}
-
-static int mlp_bwd_body(find_ctx* c, Fork& fk, const find_mlp_params* p, const Dims& d, const FwdWs& w, const BwdWs& b, const float* pos,
-						const float* lat_disp, const float* lat_col, const float* d_disp, const float* d_col, const find_mlp_grads* g, bool defer) {
+static int mlp_bwd_body(Fork& fk, const find_mlp_params* p, const Dims& d, const FwdWs& w, const BwdWs& b, const float* pos, Head* heads, const find_mlp_grads* g) {
+	find_ctx* c = fk.c;
 	hipStream_t s = fk.s;
+	const bool defer = fk.deferring;
 	const int64_t V = d.V, n_feet = d.n_feet;
-	const int ld_d0 = W + p->lat_disp, ld_c0 = W + p->lat_col;
 	const int K0 = p->in_dim + 2 * p->pe_size;
-	const bool act_d = d_disp != nullptr, act_c = d_col != nullptr;
+	Head& hd = heads[0];
+	Head& hc = heads[1];
+	const bool act_d = hd.gout != nullptr, act_c = hc.gout != nullptr;
 	// no weight-gradient buffer at all: the network is frozen (requires_grad False on every weight -- stage 3 of train.py refines the
 	// latent codes only, train.py:217-224) and the call returns the latent gradients alone
 	const bool frozen = g->trunk_w[0] == nullptr;
@@ -1233,17 +984,13 @@ static int mlp_bwd_body(find_ctx* c, Fork& fk, const find_mlp_params* p, const D
 		za.njobs = 0;
 		if (hipGetLastError() != hipSuccess) { set_error("find_mlp_bwd: zero_many_kernel launch failed"); mrc = FIND_ELAUNCH; }
 	};
-	if (!act_d) {
-		zero(g->disp_w[0], (int64_t)W * ld_d0); zero(g->disp_b[0], W);
-		for (int i = 1; i < p->n_disp; ++i) { zero(g->disp_w[i], (int64_t)W * W); zero(g->disp_b[i], W); }
-		zero(g->disp_w[p->n_disp], 3 * W); zero(g->disp_b[p->n_disp], 3);
-		if (p->lat_disp) zero(g->lat_disp, n_feet * p->lat_disp);
-	}
-	if (!act_c) {
-		zero(g->col_w[0], (int64_t)W * ld_c0); zero(g->col_b[0], W);
-		for (int i = 1; i < p->n_col; ++i) { zero(g->col_w[i], (int64_t)W * W); zero(g->col_b[i], W); }
-		zero(g->col_w[p->n_col], 3 * W); zero(g->col_b[p->n_col], 3);
-		if (p->lat_col) zero(g->lat_col, n_feet * p->lat_col);
+	for (int k = 0; k < 2; ++k) {
+		const Head& h = heads[k];
+		if (h.gout) continue;
+		zero(h.gw[0], (int64_t)W * h.ld0); zero(h.gb[0], W);
+		for (int i = 1; i < h.nl; ++i) { zero(h.gw[i], (int64_t)W * W); zero(h.gb[i], W); }
+		zero(h.gw[h.nl], 3 * W); zero(h.gb[h.nl], 3);
+		if (h.L) zero(h.glat, n_feet * h.L);
 	}
 	if (!act_d && !act_c) {
 		zero(g->trunk_w[0], (int64_t)W * K0); zero(g->trunk_b[0], W);
@@ -1258,15 +1005,14 @@ static int mlp_bwd_body(find_ctx* c, Fork& fk, const find_mlp_params* p, const D
 	// where the kernel that will run the layer cannot read the model's weight itself: bf16x3 chains (split_w_kernel, FusedStep::wmode 1) and
 	// gemm7 (Gemm2Args::w_tr) can, so a bf16x3 training step transposes nothing (round 6: this launch was 10 - 12 us in front of each of the
 	// step's two MLP backward passes)
-	const bool fused_b = use_fused(c, V, d.feet_t) && p->pe_size > 0;
-	const bool small_chain = fused_b && !d.shared;                 // the whole dX chain is one fused launch (also the frozen network's head chains)
+	const bool fused = use_fused(c, V, d.feet_t) && p->pe_size > 0;
+	const bool small_chain = fused && !d.shared;                 // the whole dX chain is one fused launch (also the frozen network's head chains)
 	const bool t_heads = !(small_chain ? chain_direct(c) : gemm7_direct(c, V, n_feet));                 // layers >= 1 of the heads
-	const bool t_trunk = !(fused_b ? chain_direct(c) : gemm7_direct(c, V, d.feet_t));                   // trunk layers >= 1
-	const bool t_first = !(fused_b && chain_direct(c));                                                  // the heads' first layers (two-operand sum: gemm3 outside a chain)
+	const bool t_trunk = !(fused ? chain_direct(c) : gemm7_direct(c, V, d.feet_t));                     // trunk layers >= 1
+	const bool t_first = !(fused && chain_direct(c));                                                    // the heads' first layers (two-operand sum: gemm3 outside a chain)
 	struct WT { const float* w; int ld; int tr; };
 	auto wt_of = [&](bool need_t, const float* orig, int ld_orig, const float* transposed) -> WT { return need_t ? WT{transposed, W, 0} : WT{orig, ld_orig, 1}; };
-	auto wt_D = [&](int l) -> WT { return l == 0 ? wt_of(t_first, p->disp_w[0], ld_d0, b.Dt[0]) : wt_of(t_heads, p->disp_w[l], W, b.Dt[l]); };
-	auto wt_C = [&](int l) -> WT { return l == 0 ? wt_of(t_first, p->col_w[0], ld_c0, b.Ct[0]) : wt_of(t_heads, p->col_w[l], W, b.Ct[l]); };
+	auto wt_H = [&](const Head& h, int l) -> WT { return l == 0 ? wt_of(t_first, h.w[0], h.ld0, h.wt[0]) : wt_of(t_heads, h.w[l], W, h.wt[l]); };
 	auto wt_T = [&](int l) -> WT { return wt_of(t_trunk, p->trunk_w[l], W, b.Tt[l]); };
 	{
 		RepackArgs ra;
@@ -1274,15 +1020,11 @@ static int mlp_bwd_body(find_ctx* c, Fork& fk, const find_mlp_params* p, const D
 		int n = 0;
 		if (!frozen) {
 			if (t_trunk) for (int i = 1; i < p->n_trunk; ++i) ra.job[n++] = RepackJob{p->trunk_w[i], b.Tt[i], W, W, W, 0, W, 1, 0, 0};
-			if (t_first) {
-				ra.job[n++] = RepackJob{p->disp_w[0], b.Dt[0], W, W, ld_d0, 0, W, 1, 0, 0};
-				ra.job[n++] = RepackJob{p->col_w[0], b.Ct[0], W, W, ld_c0, 0, W, 1, 0, 0};
-			}
+			if (t_first) for (int k = 0; k < 2; ++k) ra.job[n++] = RepackJob{heads[k].w[0], heads[k].wt[0], W, W, heads[k].ld0, 0, W, 1, 0, 0};
 		}
-		if (t_heads) {
-			for (int i = 1; i < p->n_disp; ++i) ra.job[n++] = RepackJob{p->disp_w[i], b.Dt[i], W, W, W, 0, W, 1, 0, 0};
-			for (int i = 1; i < p->n_col; ++i) ra.job[n++] = RepackJob{p->col_w[i], b.Ct[i], W, W, W, 0, W, 1, 0, 0};
-		}
+		if (t_heads)
+			for (int k = 0; k < 2; ++k)
+				for (int i = 1; i < heads[k].nl; ++i) ra.job[n++] = RepackJob{heads[k].w[i], heads[k].wt[i], W, W, W, 0, W, 1, 0, 0};
 		ra.njobs = n;
 		if (n > 0) hipLaunchKernelGGL(repack_kernel, dim3(64, n), dim3(256), 0, s, ra);
 		FIND_LAUNCH_CHECK("repack_kernel(T)");
@@ -1294,30 +1036,29 @@ static int mlp_bwd_body(find_ctx* c, Fork& fk, const find_mlp_params* p, const D
 	const bool a16 = (note16 & 1) != 0;   // (the forward stored w.D / w.C as fp16: b.dzD / b.dzC follow)
 	const bool fold = (note16 & 2) != 0;  // (... and did not store w.D[0] / w.C[0] at all: their readers form them from w.hp / w.hp2 and the bias rows)
 	struct Virt { const float* P; const float* bias; int64_t bstride; };
-	auto virt = [&](bool colour, int l) -> Virt {   // the input of head layer l (l >= 1): virtual for l == 1 under bcast_fold
+	auto virt = [&](const Head& h, int l) -> Virt {   // the input of head layer l (l >= 1): virtual for l == 1 under bcast_fold
 		if (!fold || l != 1) return Virt{nullptr, nullptr, 0};
-		if (colour) return (p->lat_col > 0) ? Virt{w.hp2, w.fbc, W} : Virt{w.hp2, p->col_b[0], 0};
-		return (p->lat_disp > 0) ? Virt{w.hp, w.fbd, W} : Virt{w.hp, p->disp_b[0], 0};
+		return Virt{h.hp, h.bias0, h.bstride0};
 	};
-	int cd = 0, cc = 0;  // current dZ buffer per head
 	{
 		HeadOutBwdArgs h;
 		memset(&h, 0, sizeof(h));
-		h.y[0] = w.D[p->n_disp - 1]; h.y[1] = w.C[p->n_col - 1];
-		h.w[0] = p->disp_w[p->n_disp]; h.w[1] = p->col_w[p->n_col];
-		h.z[0] = w.zd; h.z[1] = w.zc;
-		h.gout[0] = d_disp; h.gout[1] = d_col;
-		h.dy[0] = b.dzD[cd]; h.dy[1] = b.dzC[cc];
-		h.pw[0] = b.pwo[0]; h.pw[1] = b.pwo[1];
-		h.pb[0] = b.pbo[0]; h.pb[1] = b.pbo[1];
+		HeadOutReduceArgs hr;
+		memset(&hr, 0, sizeof(hr));
+		for (int k = 0; k < 2; ++k) {
+			const Head& hk = heads[k];
+			h.y[k] = hk.act[hk.nl - 1];
+			h.w[k] = hk.w[hk.nl];
+			h.z[k] = hk.z;
+			h.gout[k] = hk.gout;
+			h.dy[k] = hk.dz[hk.cur];
+			h.pw[k] = b.pwo[k]; h.pb[k] = b.pbo[k];
+			hr.pw[k] = b.pwo[k]; hr.pb[k] = b.pbo[k];
+			hr.dw[k] = hk.gout ? hk.gw[hk.nl] : nullptr; hr.db[k] = hk.gb[hk.nl];
+		}
 		h.rows = d.rows_h;
 		h.half = a16 ? 1 : 0;
 		hipLaunchKernelGGL(head_out_bwd_kernel, dim3((unsigned)b.nblk_out, 2), dim3(256), 0, s, h);
-		HeadOutReduceArgs hr;
-		memset(&hr, 0, sizeof(hr));
-		hr.pw[0] = b.pwo[0]; hr.pw[1] = b.pwo[1]; hr.pb[0] = b.pbo[0]; hr.pb[1] = b.pbo[1];
-		hr.dw[0] = act_d ? g->disp_w[p->n_disp] : nullptr; hr.db[0] = g->disp_b[p->n_disp];
-		hr.dw[1] = act_c ? g->col_w[p->n_col] : nullptr; hr.db[1] = g->col_b[p->n_col];
 		hr.nblk = b.nblk_out;
 		// (the 3-wide layers' dW / db feed nothing of the dX chain: their reduce goes to a side stream like every other weight gradient --
 		// it used to sit between head_out_bwd and the first dX GEMM of both backward passes of a step, 10 - 14 us each)
@@ -1331,106 +1072,127 @@ static int mlp_bwd_body(find_ctx* c, Fork& fk, const find_mlp_params* p, const D
 	const float* hl = w.H[p->n_trunk - 1];
 	const int64_t hl_stride = d.shared ? 0 : V * W;
 
-	const bool fused = use_fused(c, V, d.feet_t) && p->pe_size > 0;
-	// The trunk's dX chain of a call whose heads are large (the shared template of a batch: launched far below, behind the heads' GEMMs) is
-	// put together HERE, so that its weights are split (chain_prepare) before the large kernels fill the chip.
-	Chain tch;
-	if (fused && !frozen && d.shared) {
-		WT Wt[2]; int nb = 0;
-		if (act_d) Wt[nb++] = wt_D(0);
-		if (act_c) Wt[nb++] = wt_C(0);
+	// ---- pieces of the dX chain and of the gradients around it, shared by the paths below
+	// a head's hidden layers, last down to the second, as steps of a fused chain
+	auto head_chain = [&](Chain& ch, Head& h) {
+		for (int l = h.nl - 1; l >= 1; --l) {
+			const WT t = wt_H(h, l);
+			FusedStep& st = ch.gemm(t.w, t.ld, W / KC, h.cur == 0 ? h.dz[0] : nullptr);
+			st.wmode = (unsigned char)t.tr;
+			st.mask = 1; st.aux = h.act[l - 1]; st.dst = h.dz[h.cur + 1]; st.to_lds = 1;
+			h.cur += 1;
+		}
+	};
+	// gradient wrt the trunk output: both heads summed in one accumulator (the displacement head's operand first), then masked by the
+	// trunk's last activation
+	auto trunk_out_steps = [&](Chain& ch, const float* dz_d, const float* dz_c) {
+		const float* A[2]; WT Wt[2]; int nb = 0;
+		if (act_d) { A[nb] = dz_d; Wt[nb] = wt_H(hd, 0); ++nb; }
+		if (act_c) { A[nb] = dz_c; Wt[nb] = wt_H(hc, 0); ++nb; }
 		for (int i = 0; i < nb; ++i) {
-			FusedStep& st = tch.gemm(Wt[i].w, Wt[i].ld, W / KC, hl /* patched below: the head's foot-summed first-layer dZ */);
+			FusedStep& st = ch.gemm(Wt[i].w, Wt[i].ld, W / KC, A[i]);
 			st.wmode = (unsigned char)Wt[i].tr;
 			st.accum = i > 0;
 			if (i + 1 < nb) { st.keep = 1; continue; }
 			st.mask = 1; st.aux = hl; st.dst = b.dzT[0]; st.to_lds = 1;
 		}
+	};
+	auto trunk_steps = [&](Chain& ch) {
 		for (int l = p->n_trunk - 1; l >= 1; --l) {
 			const WT t = wt_T(l);
-			FusedStep& st = tch.gemm(t.w, t.ld, W / KC);
+			FusedStep& st = ch.gemm(t.w, t.ld, W / KC);
 			st.wmode = (unsigned char)t.tr;
 			st.mask = 1; st.aux = w.H[l - 1]; st.dst = b.dzT[p->n_trunk - l]; st.to_lds = 1;
 		}
+	};
+	// masked dX:  y = (dz @ W) * (mask > 0), with W given pre-transposed or -- t.tr -- as the model holds it
+	// (v.bias: bcast_fold -- mask is the shared fp32 product P and the layer's output was relu(P[v] + v.bias[foot]))
+	auto dx_args = [&](const float* dz, const WT& t, const float* mask, float* y, const Virt& v) {
+		Gemm2Args a = gemm_args();
+		a.a0 = dz; a.a_foot_stride = V * W; a.lda = W;
+		a.w0 = t.w; a.ldw = t.ld; a.w_tr = t.tr; a.nchunk = W / KC;
+		a.mask = mask; a.mask_foot_stride = v.bias ? 0 : V * W;
+		a.vm_bias = v.bias; a.vm_bias_stride = v.bstride;
+		a.y = y; a.y_foot_stride = V * W; a.ldy = W; a.V = (int)V;
+		return a;
+	};
+	// weight gradient of a 256-wide layer (the caller adds what its path needs: stream, sums, virtual operand)
+	auto layer_wgrad = [&](const float* dz, const float* x, int64_t x_foot_stride, int64_t feet, float* dw, float* db) {
+		Wgrad wg;
+		wg.dz = dz; wg.x = x; wg.x_foot_stride = x_foot_stride; wg.feet = feet; wg.V = V; wg.dw = dw; wg.db = db;
+		return wg;
+	};
+	// the Fourier layer's weight gradient, on side stream `side` out of slab set `set`
+	auto fourier_wgrad = [&](const float* dz, int side, int set) -> int {
+		Wgrad wg;
+		wg.dz = dz; wg.pos = pos; wg.pos_foot_stride = V * 3; wg.nkt = d.nkt0; wg.feet = d.feet_t; wg.V = V;
+		wg.dw = g->trunk_w[0]; wg.ld_out = K0; wg.k_valid = 0; wg.pe_map = 1; wg.db = g->trunk_b[0];
+		wg.s = fk.stream(side);
+		return weight_grad(c, &fk, p, wg, slabs(b, set));
+	};
+	// per-foot column sums of a head's first-layer dZ (and, zs given, its sum over the feet): partial sums on the caller's stream, then
+	// their reduce (of nblk blocks) on the stream of whoever reads S
+	auto foot_partials = [&](const Head& h, float* zs) {
+		hipLaunchKernelGGL(footsum_kernel, dim3((unsigned)b.nblk_fs * 4), dim3(256), 0, s, h.dz[h.cur], (int)n_feet, (int)V, zs, h.pS, a16 ? 1 : 0);
+	};
+	auto foot_reduce = [&](const Head& h, int nblk, hipStream_t st) {
+		hipLaunchKernelGGL(footsum_reduce_kernel, dim3((unsigned)n_feet, 4), dim3(1024), 0, st, h.pS, nblk, (int)n_feet, h.S);
+	};
+	// d loss / d latent[foot] = S[foot] . W0[:, 256:]; with gw0 also the latent columns of the first layer's dW, with db_late its bias gradient
+	auto latent_grad = [&](const Head& h, float* gw0, float* db_late, hipStream_t st) {
+		hipLaunchKernelGGL(latent_grad_kernel, dim3((unsigned)(n_feet + (gw0 ? W : 0) + (db_late ? 1 : 0))), dim3(256), 0, st, h.w[0], h.ld0, h.lat, h.L, h.S, (int)n_feet,
+						   h.glat, gw0, db_late);
+	};
+
+	// The trunk's dX chain of a call whose heads are large (the shared template of a batch: launched far below, behind the heads' GEMMs) is
+	// put together HERE, so that its weights are split (chain_prepare) before the large kernels fill the chip.
+	Chain tch;
+	if (fused && !frozen && d.shared) {
+		trunk_out_steps(tch, hd.zs, hc.zs);   // (the heads' foot-summed first-layer dZ)
+		trunk_steps(tch);
 		FIND_TRY(chain_prepare(c, tch, V, d.feet_t, s, b.w6, chain_w6_bytes(p)));
 	}
 	if (frozen) {
 		// ---- latents only.  d loss / d latent[foot] = (sum_v dZ0[foot, v]) . W0[:, 256:]: the heads' dX chains down to their first layers,
 		// per-foot column sums, one small product per head.  Nothing reaches the trunk, no weight gradient is formed: at the reference's
 		// batch size this backward is 4 of the 9 layer-steps of the full chain and none of its thirteen weight-gradient jobs.
-		const bool want_d = act_d && p->lat_disp > 0 && g->lat_disp != nullptr, want_c = act_c && p->lat_col > 0 && g->lat_col != nullptr;
-		if (!want_d && !want_c) return FIND_OK;
-		if (fused && !d.shared) {
+		auto want = [&](const Head& h) { return h.gout && h.L > 0 && h.glat != nullptr; };
+		if (!want(hd) && !want(hc)) return FIND_OK;
+		if (small_chain) {
 			Chain ch;
-			int nsteps = 0;
-			auto head_chain = [&](int nl, float* const* act, float* const* dzbuf, bool colour, int& cur) {
-				for (int l = nl - 1; l >= 1; --l) {
-					const WT t = colour ? wt_C(l) : wt_D(l);
-					FusedStep& st = ch.gemm(t.w, t.ld, W / KC, cur == 0 ? dzbuf[0] : nullptr);
-					st.wmode = (unsigned char)t.tr;
-					st.mask = 1; st.aux = act[l - 1]; st.dst = dzbuf[cur + 1]; st.to_lds = 1;
-					cur += 1; nsteps += 1;
-				}
-			};
-			if (want_c) head_chain(p->n_col, w.C, b.dzC, true, cc);
-			if (want_d) head_chain(p->n_disp, w.D, b.dzD, false, cd);
-			if (nsteps > 0) FIND_TRY(launch_chain(c, ch, V, d.feet_t, s, b.w6, chain_w6_bytes(p)));
+			if (want(hc)) head_chain(ch, hc);
+			if (want(hd)) head_chain(ch, hd);
+			if (ch.a.n_steps > 0) FIND_TRY(launch_chain(c, ch, V, d.feet_t, s, b.w6, chain_w6_bytes(p)));
 		} else {
-			if (want_d) for (int l = p->n_disp - 1; l >= 1; --l) { const WT t = wt_D(l); const Virt v = virt(false, l); FIND_TRY(linear_bwd_dx(c, b.dzD[cd], t.w, t.ld, t.tr, v.P ? v.P : w.D[l - 1], b.dzD[cd + 1], V, n_feet, s, a16, v.bias, v.bstride)); cd += 1; }
-			if (want_c) for (int l = p->n_col - 1; l >= 1; --l) { const WT t = wt_C(l); const Virt v = virt(true, l); FIND_TRY(linear_bwd_dx(c, b.dzC[cc], t.w, t.ld, t.tr, v.P ? v.P : w.C[l - 1], b.dzC[cc + 1], V, n_feet, s, a16, v.bias, v.bstride)); cc += 1; }
+			for (int k = 0; k < 2; ++k) {
+				Head& h = heads[k];
+				if (!want(h)) continue;
+				for (int l = h.nl - 1; l >= 1; --l) {
+					const Virt v = virt(h, l);
+					FIND_TRY(launch_gemm(c, AMODE_MAT, EPI_MASK, dx_args(h.dz[h.cur], wt_H(h, l), v.P ? v.P : h.act[l - 1], h.dz[h.cur + 1], v), n_feet, s, a16));
+					h.cur += 1;
+				}
+			}
 		}
-		struct Job { const float* dz; float* ps; float* S; const float* w0; int ld0; const float* lat; int L; float* glat; };
-		const Job jobs[2] = {{b.dzD[cd], b.pS, b.Sd, p->disp_w[0], ld_d0, lat_disp, p->lat_disp, g->lat_disp},
-							 {b.dzC[cc], b.pS2, b.Sc, p->col_w[0], ld_c0, lat_col, p->lat_col, g->lat_col}};
-		for (int h = 0; h < 2; ++h) {
-			if (!(h == 0 ? want_d : want_c)) continue;
-			const Job& j = jobs[h];
-			hipLaunchKernelGGL(footsum_kernel, dim3((unsigned)b.nblk_fs * 4), dim3(256), 0, s, j.dz, (int)n_feet, (int)V, (float*)nullptr, j.ps, a16 ? 1 : 0);
-			hipLaunchKernelGGL(footsum_reduce_kernel, dim3((unsigned)n_feet, 4), dim3(1024), 0, s, j.ps, b.nblk_fs, (int)n_feet, j.S);
-			hipLaunchKernelGGL(latent_grad_kernel, dim3((unsigned)n_feet), dim3(256), 0, s, j.w0, j.ld0, j.lat, j.L, j.S, (int)n_feet, j.glat,
-							   (float*)nullptr, (float*)nullptr);
+		for (int k = 0; k < 2; ++k) {
+			const Head& h = heads[k];
+			if (!want(h)) continue;
+			foot_partials(h, nullptr);
+			foot_reduce(h, b.nblk_fs, s);
+			latent_grad(h, nullptr, nullptr, s);
 			FIND_LAUNCH_CHECK("latent gradients of a frozen network");
 		}
 		return FIND_OK;
 	}
-	if (fused && !d.shared) {
+	if (small_chain) {
 		// ---- small call (every layer has few rows: the reference's batch 1, the texture samples): the whole dX chain of both heads and
 		// the trunk is ONE fused launch (mlp_fused.h); every layer's dZ lands in its own buffer, and the weight gradients follow on the
 		// side streams (round-robin, one slab set per stream)
 		Chain ch;
-		int cd2 = 0, cc2 = 0;
-		auto head_chain = [&](int nl, float* const* act, float* const* dzbuf, bool colour, int& cur) {
-			for (int l = nl - 1; l >= 1; --l) {
-				const WT t = colour ? wt_C(l) : wt_D(l);
-				FusedStep& st = ch.gemm(t.w, t.ld, W / KC, cur == 0 ? dzbuf[0] : nullptr);
-				st.wmode = (unsigned char)t.tr;
-				st.mask = 1; st.aux = act[l - 1]; st.dst = dzbuf[cur + 1]; st.to_lds = 1;
-				cur += 1;
-			}
-		};
-		if (act_c) head_chain(p->n_col, w.C, b.dzC, true, cc2);
-		if (act_d) head_chain(p->n_disp, w.D, b.dzD, false, cd2);
-		{
-			// gradient wrt the trunk output: both heads summed in one accumulator, then masked by the trunk's last activation
-			const float* A[2]; WT Wt[2]; int nb = 0;
-			if (act_d) { A[nb] = b.dzD[cd2]; Wt[nb] = wt_D(0); ++nb; }
-			if (act_c) { A[nb] = b.dzC[cc2]; Wt[nb] = wt_C(0); ++nb; }
-			for (int i = 0; i < nb; ++i) {
-				FusedStep& st = ch.gemm(Wt[i].w, Wt[i].ld, W / KC, A[i]);
-				st.wmode = (unsigned char)Wt[i].tr;
-				st.accum = i > 0;
-				if (i + 1 < nb) { st.keep = 1; continue; }
-				st.mask = 1; st.aux = hl; st.dst = b.dzT[0]; st.to_lds = 1;
-			}
-		}
-		int ct2 = 0;
-		for (int l = p->n_trunk - 1; l >= 1; --l) {
-			const WT t = wt_T(l);
-			FusedStep& st = ch.gemm(t.w, t.ld, W / KC);
-			st.wmode = (unsigned char)t.tr;
-			st.mask = 1; st.aux = w.H[l - 1]; st.dst = b.dzT[ct2 + 1]; st.to_lds = 1;
-			ct2 += 1;
-		}
+		if (act_c) head_chain(ch, hc);   // (the colour head's layers first)
+		if (act_d) head_chain(ch, hd);
+		trunk_out_steps(ch, hd.dz[hd.cur], hc.dz[hc.cur]);
+		trunk_steps(ch);
 		FIND_TRY(launch_chain(c, ch, V, d.feet_t, s, b.w6, chain_w6_bytes(p)));
 		// weight gradients: all inputs exist now.  fp32: every 256 x 256 layer in ONE grouped launch (+ one grouped slab reduce) on a side
 		// stream, the Fourier layer on another; the opt-in fp16 mode keeps its per-layer dw3 launches.
@@ -1438,41 +1200,36 @@ static int mlp_bwd_body(find_ctx* c, Fork& fk, const find_mlp_params* p, const D
 		WgradGroup G;
 		G.live_jobs = (act_d ? p->n_disp : 0) + (act_c ? p->n_col : 0) + (p->n_trunk - 1);
 		int rr = 0;
-		auto next_side = [&](BwdWs* bk) -> int {
+		auto one = [&](Wgrad wg) -> int {
+			if (grouped) return wgrad_group_add(c, G, b, wg);
 			const int k = fk.on ? 1 + rr % 2 : 0;
 			rr += 1;
-			*bk = b;
-			bk->pw = b.pw_t[k]; bk->pb = b.pb_t[k];
 			fk.fork_to(k);
-			return k;
+			wg.s = fk.stream(k);
+			return weight_grad(c, &fk, p, wg, slabs(b, k));
 		};
-		auto one = [&](const float* dz, const float* x, int64_t xs, int64_t feet, float* dw, int ld_out, float* db, float* S) -> int {
-			if (grouped) return wgrad_group_add(c, G, b, dz, x, xs, feet, V, dw, ld_out, db, S);
-			BwdWs bk; const int k = next_side(&bk);
-			return weight_grad(c, &fk, dz, x, xs, nullptr, 0, p, 1, feet, V, bk, dw, ld_out, W, 0, db, S, fk.stream(k));
-		};
-		struct Lat { const float* w0full; int ld0; const float* lat; int L; float* S; float* glat; float* gw0; };
-		Lat lats[2]; int nlat = 0;
-		auto head_wgrads = [&](int nl, float* const* act, float* const* dzbuf, int cur_last, float* const* gw, float* const* gb, const float* w0full, int ld0,
-							   const float* lat, int L, float* S, float* glat) -> int {
-			for (int l = nl - 1; l >= 1; --l) FIND_TRY(one(dzbuf[nl - 1 - l], act[l - 1], V * W, n_feet, gw[l], W, gb[l], nullptr));
-			if (defer && L > 0) {
+		const Head* lats[2]; int nlat = 0;
+		auto head_wgrads = [&](const Head& h) -> int {
+			for (int l = h.nl - 1; l >= 1; --l) FIND_TRY(one(layer_wgrad(h.dz[h.nl - 1 - l], h.act[l - 1], V * W, n_feet, h.gw[l], h.gb[l])));
+			if (defer && h.L > 0) {
 				// the weight gradients stay behind on the side streams: the latent gradients -- an OUTPUT autograd hands to whatever comes
 				// next -- are formed on the caller's stream, from per-foot column sums of their own (no slab reduce to wait for)
-				float* ps = (gw == g->disp_w) ? b.pS : b.pS2;
-				hipLaunchKernelGGL(footsum_kernel, dim3((unsigned)b.nblk_fs * 4), dim3(256), 0, s, dzbuf[cur_last], (int)n_feet, (int)V, (float*)nullptr, ps, 0);
-				hipLaunchKernelGGL(footsum_reduce_kernel, dim3((unsigned)n_feet, 4), dim3(1024), 0, s, ps, b.nblk_fs, (int)n_feet, S);
-				hipLaunchKernelGGL(latent_grad_kernel, dim3((unsigned)(n_feet + W)), dim3(256), 0, s, w0full, ld0, lat, L, S, (int)n_feet, glat, gw[0], (float*)nullptr);
+				foot_partials(h, nullptr);
+				foot_reduce(h, b.nblk_fs, s);
+				latent_grad(h, h.gw[0], nullptr, s);
 				FIND_LAUNCH_CHECK("latent gradients (deferred join)");
 			}
-			FIND_TRY(one(dzbuf[cur_last], hl, hl_stride, n_feet, gw[0], ld0, gb[0], (L > 0 && !defer) ? S : nullptr));
-			if (L > 0 && !defer) lats[nlat++] = Lat{w0full, ld0, lat, L, S, glat, gw[0]};
+			Wgrad wg = layer_wgrad(h.dz[h.cur], hl, hl_stride, n_feet, h.gw[0], h.gb[0]);
+			wg.ld_out = h.ld0;
+			wg.S = (h.L > 0 && !defer) ? h.S : nullptr;
+			FIND_TRY(one(wg));
+			if (h.L > 0 && !defer) lats[nlat++] = &h;
 			return FIND_OK;
 		};
-		if (act_d) FIND_TRY(head_wgrads(p->n_disp, w.D, b.dzD, cd2, g->disp_w, g->disp_b, p->disp_w[0], ld_d0, lat_disp, p->lat_disp, b.Sd, g->lat_disp));
-		if (act_c) FIND_TRY(head_wgrads(p->n_col, w.C, b.dzC, cc2, g->col_w, g->col_b, p->col_w[0], ld_c0, lat_col, p->lat_col, b.Sc, g->lat_col));
+		if (act_d) FIND_TRY(head_wgrads(hd));
+		if (act_c) FIND_TRY(head_wgrads(hc));
 		for (int l = p->n_trunk - 1; l >= 1; --l)
-			FIND_TRY(one(b.dzT[p->n_trunk - 1 - l], w.H[l - 1], V * W, d.feet_t, g->trunk_w[l], W, g->trunk_b[l], nullptr));
+			FIND_TRY(one(layer_wgrad(b.dzT[p->n_trunk - 1 - l], w.H[l - 1], V * W, d.feet_t, g->trunk_w[l], g->trunk_b[l])));
 		// the latent gradients read the per-foot column sums S (written by the slab reduce): same stream, behind it
 		hipStream_t sl = s;
 		if (grouped) {
@@ -1485,14 +1242,13 @@ static int mlp_bwd_body(find_ctx* c, Fork& fk, const find_mlp_params* p, const D
 			sl = fk.stream(1);
 		}
 		for (int i = 0; i < nlat; ++i) {
-			hipLaunchKernelGGL(latent_grad_kernel, dim3((unsigned)(n_feet + W)), dim3(256), 0, sl, lats[i].w0full, lats[i].ld0, lats[i].lat, lats[i].L, lats[i].S,
-							   (int)n_feet, lats[i].glat, lats[i].gw0, (float*)nullptr);
+			latent_grad(*lats[i], lats[i]->gw[0], nullptr, sl);
 			FIND_LAUNCH_CHECK("latent_grad_kernel");
 		}
 		{
 			const int k = fk.on ? 2 : 0;
 			fk.fork_to(k);
-			FIND_TRY(weight_grad(c, &fk, b.dzT[ct2], nullptr, 0, pos, V * 3, p, d.nkt0, d.feet_t, V, b, g->trunk_w[0], K0, 0, 1, g->trunk_b[0], nullptr, fk.stream(k)));
+			FIND_TRY(fourier_wgrad(b.dzT[p->n_trunk - 1], k, 0));
 		}
 		FIND_LAUNCH_CHECK("find_mlp_bwd");
 		return FIND_OK;
@@ -1507,14 +1263,14 @@ static int mlp_bwd_body(find_ctx* c, Fork& fk, const find_mlp_params* p, const D
 	WgradGroup G;
 	const bool grouped_v = fused && d.shared && !c->f16 && b.grp_pw != nullptr;
 	G.live_jobs = (p->n_trunk - 1) + (act_d ? 1 : 0) + (act_c ? 1 : 0);
-	auto head_bwd = [&](int nl, float* const* act, float* const* dzbuf, int& cur, bool colour, float* const* gw, float* const* gb,
-						const float* w0full, int ld0, const float* lat, int L, float* S, float* glat, float* zs, float* ps, int side) -> int {
+	auto head_bwd = [&](Head& h) -> int {
 		int fsum_pairs = 0;
-		for (int l = nl - 1; l >= 1; --l) {
-			const Virt v = virt(colour, l);
-			const float* const xin = v.P ? v.P : act[l - 1];
-			const int64_t xin_stride = v.P ? 0 : V * W;
+		for (int l = h.nl - 1; l >= 1; --l) {
+			const Virt v = virt(h, l);
+			const float* const xin = v.P ? v.P : h.act[l - 1];
 			fk.fork_to(Q);
+			Wgrad wg = layer_wgrad(h.dz[h.cur], xin, v.P ? 0 : V * W, n_feet, h.gw[l], h.gb[l]);
+			wg.s = fk.stream(Q); wg.h16 = a16; wg.vx_bias = v.bias; wg.vx_bias_stride = v.bstride;
 			// the large layers alternate between two slab sets and hand their slab reduce to stream R: the reduce (LDS-using, so
 			// it only gets a CU when a ring kernel's workgroup retires) no longer sits between two dw2 launches on Q
 			// (Not under stream capture: there the streams only express dependencies and the graph executor schedules the branches;
@@ -1522,110 +1278,97 @@ static int mlp_bwd_body(find_ctx* c, Fork& fk, const find_mlp_params* p, const D
 			if (fk.on && c->reduce_stream && !fk.capturing) {
 				const int si = big_toggle & 1;
 				big_toggle += 1;
-				BwdWs bk = b;
-				bk.pw = b.pw_t[si ? 3 : 0]; bk.pb = b.pb_t[si ? 3 : 0];
 				fk.wait(Q, set_free[si]);
-				FIND_TRY(weight_grad(c, &fk, dzbuf[cur], xin, xin_stride, nullptr, 0, p, 1, n_feet, V, bk, gw[l], W, W, 0, gb[l], nullptr, fk.stream(Q), Q, R, a16, v.bias, v.bstride));
+				wg.s_side = Q; wg.reduce_side = R;
+				FIND_TRY(weight_grad(c, &fk, p, wg, slabs(b, si ? 3 : 0)));
 				set_free[si] = fk.mark(R);
 			} else {
-				FIND_TRY(weight_grad(c, &fk, dzbuf[cur], xin, xin_stride, nullptr, 0, p, 1, n_feet, V, b, gw[l], W, W, 0, gb[l], nullptr, fk.stream(Q), -1, -1, a16, v.bias, v.bstride));
+				FIND_TRY(weight_grad(c, &fk, p, wg, slabs(b, 0)));
 			}
-			const WT t = colour ? wt_C(l) : wt_D(l);
 			// footsum_fold: this dX GEMM's output is the broadcast layer's dZ, of which only sums are read (below): formed inside the GEMM
-			fsum_pairs = (l == 1 && v.P && !a16 && c->footsum_fold && zs != nullptr && gemm7_direct(c, V, n_feet)) ? gemm7_fsum_pairs(c, V, n_feet) : 0;
-			if (fsum_pairs > 0) {
-				float* const fs1 = colour ? b.fs1C : b.fs1D;
-				FIND_TRY(linear_bwd_dx(c, dzbuf[cur], t.w, t.ld, t.tr, xin, dzbuf[cur + 1], V, n_feet, s, a16, v.bias, v.bstride, zs, fs1 - zs, ps));
-			} else {
-				FIND_TRY(linear_bwd_dx(c, dzbuf[cur], t.w, t.ld, t.tr, xin, dzbuf[cur + 1], V, n_feet, s, a16, v.bias, v.bstride));
-			}
-			cur += 1;
+			fsum_pairs = (l == 1 && v.P && !a16 && c->footsum_fold && h.zs != nullptr && gemm7_direct(c, V, n_feet)) ? gemm7_fsum_pairs(c, V, n_feet) : 0;
+			Gemm2Args a = dx_args(h.dz[h.cur], wt_H(h, l), xin, h.dz[h.cur + 1], v);
+			if (fsum_pairs > 0) { a.fs_out = h.zs; a.fs_slot_stride = h.fs1 - h.zs; a.cs_out = h.pS; }   // (y is then not written)
+			FIND_TRY(launch_gemm(c, AMODE_MAT, EPI_MASK, a, n_feet, s, a16));
+			h.cur += 1;
 		}
 		float* db_late = nullptr;
 		hipStream_t q0;
-		if (d.shared && fsum_pairs > 0) {
-			// (the two partial foot sums -> the foot sum; the per-foot column sums wait in `ps`, one block per workgroup pair of the GEMM)
-			const int64_t n4 = V * W / 4;
-			hipLaunchKernelGGL(add_inplace_kernel, dim3((unsigned)cdiv(n4, 256)), dim3(256), 0, s, zs, colour ? b.fs1C : b.fs1D, n4);
-			fk.fork_to(side);
-			q0 = fk.stream(side);
-			hipLaunchKernelGGL(footsum_reduce_kernel, dim3((unsigned)n_feet, 4), dim3(1024), 0, q0, ps, fsum_pairs, (int)n_feet, S);
-			if (L > 0) db_late = gb[0];
-			else hipLaunchKernelGGL(colsum_small_kernel, dim3(1), dim3(256), 0, q0, S, (int)n_feet, gb[0]);
-			FIND_LAUNCH_CHECK("footsum (folded)");
-			BwdWs bk = b;
-			bk.pw = b.pw_t[side]; bk.pb = b.pb_t[side];
-			if (grouped_v) FIND_TRY(wgrad_group_add(c, G, b, zs, hl, 0, 1, V, gw[0], ld0, nullptr, nullptr));
-			else FIND_TRY(weight_grad(c, &fk, zs, hl, 0, nullptr, 0, p, 1, 1, V, bk, gw[0], ld0, W, 0, nullptr, nullptr, q0));
-		} else if (d.shared) {
+		if (d.shared) {
 			// every foot multiplies the same trunk rows: reduce dZ0 over feet first (one pass), then M = V GEMMs
 			// (Measured and dropped: the foot sum on the head's side stream, the caller's stream going straight on to the other head's dX
 			// chain and waiting for the sums in step 4 -- 3.49 against 3.38 ms per train_3d step: the HBM-bound pass beside the dX GEMMs
 			// costs them more than the wait it removes.)
-			hipLaunchKernelGGL(footsum_kernel, dim3((unsigned)b.nblk_fs * 4), dim3(256), 0, s, dzbuf[cur], (int)n_feet, (int)V, zs, ps, a16 ? 1 : 0);
 			// the foot-summed first layer is a small launch: its own side stream and slab set, so that it does not queue behind the
 			// large weight-gradient launches on Q.  The per-foot column sums go there too: only the latent / bias gradients read them.
-			fk.fork_to(side);
-			q0 = fk.stream(side);
-			BwdWs bk = b;
-			bk.pw = b.pw_t[side]; bk.pb = b.pb_t[side];
-			hipLaunchKernelGGL(footsum_reduce_kernel, dim3((unsigned)n_feet, 4), dim3(1024), 0, q0, ps, b.nblk_fs, (int)n_feet, S);
+			if (fsum_pairs > 0) {
+				// (footsum_fold: the two partial foot sums -> the foot sum; the per-foot column sums wait in pS, one block per workgroup pair of the GEMM)
+				const int64_t n4 = V * W / 4;
+				hipLaunchKernelGGL(add_inplace_kernel, dim3((unsigned)cdiv(n4, 256)), dim3(256), 0, s, h.zs, h.fs1, n4);
+			} else {
+				foot_partials(h, h.zs);
+			}
+			fk.fork_to(h.side);
+			q0 = fk.stream(h.side);
+			foot_reduce(h, fsum_pairs > 0 ? fsum_pairs : b.nblk_fs, q0);
 			// (the bias gradient -- S summed over feet -- rides along with the latent-gradient launch when there is one)
-			if (L > 0) db_late = gb[0];
-			else hipLaunchKernelGGL(colsum_small_kernel, dim3(1), dim3(256), 0, q0, S, (int)n_feet, gb[0]);
+			if (h.L > 0) db_late = h.gb[0];
+			else hipLaunchKernelGGL(colsum_small_kernel, dim3(1), dim3(256), 0, q0, h.S, (int)n_feet, h.gb[0]);
 			FIND_LAUNCH_CHECK("footsum");
-			if (grouped_v) FIND_TRY(wgrad_group_add(c, G, b, zs, hl, 0, 1, V, gw[0], ld0, nullptr, nullptr));
-			else FIND_TRY(weight_grad(c, &fk, zs, hl, 0, nullptr, 0, p, 1, 1, V, bk, gw[0], ld0, W, 0, nullptr, nullptr, q0));
+			Wgrad wg = layer_wgrad(h.zs, hl, 0, 1, h.gw[0], nullptr);
+			wg.ld_out = h.ld0;
+			wg.s = q0;
+			if (grouped_v) FIND_TRY(wgrad_group_add(c, G, b, wg));
+			else FIND_TRY(weight_grad(c, &fk, p, wg, slabs(b, h.side)));
 		} else {
 			fk.fork_to(Q);
 			q0 = fk.stream(Q);
 			fk.wait(Q, set_free[0]);   // set 0 may still be read by a reduce on R
-			FIND_TRY(weight_grad(c, &fk, dzbuf[cur], hl, hl_stride, nullptr, 0, p, 1, n_feet, V, b, gw[0], ld0, W, 0, gb[0], (L > 0) ? S : nullptr, q0));
+			Wgrad wg = layer_wgrad(h.dz[h.cur], hl, hl_stride, n_feet, h.gw[0], h.gb[0]);
+			wg.ld_out = h.ld0;
+			wg.S = (h.L > 0) ? h.S : nullptr;
+			wg.s = q0;
+			FIND_TRY(weight_grad(c, &fk, p, wg, slabs(b, 0)));
 		}
-		if (L > 0) {
-			hipLaunchKernelGGL(latent_grad_kernel, dim3((unsigned)(n_feet + W + (db_late ? 1 : 0))), dim3(256), 0, q0, w0full, ld0, lat, L, S, (int)n_feet, glat,
-							   gw[0], db_late);
+		if (h.L > 0) {
+			latent_grad(h, h.gw[0], db_late, q0);
 			FIND_LAUNCH_CHECK("latent_grad_kernel");
 		}
 		return FIND_OK;
 	};
-	if (act_d) FIND_TRY(head_bwd(p->n_disp, w.D, b.dzD, cd, false, g->disp_w, g->disp_b, p->disp_w[0], ld_d0, lat_disp, p->lat_disp, b.Sd, g->lat_disp, b.zsD, b.pS, T1));
-	if (act_c) FIND_TRY(head_bwd(p->n_col, w.C, b.dzC, cc, true, g->col_w, g->col_b, p->col_w[0], ld_c0, lat_col, p->lat_col, b.Sc, g->lat_col, b.zsC, b.pS2, T2));
+	if (act_d) FIND_TRY(head_bwd(hd));
+	if (act_c) FIND_TRY(head_bwd(hc));
 
 	// 4 + 5.  gradient wrt the trunk output -- both heads (and, for a shared trunk, every foot) summed in the K loop -- and the trunk's
 	// dX chain.  With few trunk rows (the shared template) all of it is one fused launch; the weight gradients follow on T1 / T2.
+	// a trunk layer's weight gradient: into the grouped launch, or -- independent of each other, each filling a fraction of the chip --
+	// alternating between T1 and T2 (own slab set each)
+	auto trunk_wgrad = [&](int l, const float* dz) -> int {
+		Wgrad wg = layer_wgrad(dz, w.H[l - 1], V * W, d.feet_t, g->trunk_w[l], g->trunk_b[l]);
+		if (grouped_v) return wgrad_group_add(c, G, b, wg);
+		const int k = fk.on ? 1 + (l & 1) : 0;
+		fk.fork_to(k);
+		wg.s = fk.stream(k);
+		return weight_grad(c, &fk, p, wg, slabs(b, k));
+	};
 	int ct = 0;
 	if (fused) {
-		Chain& ch = tch;   // (built, and its weights split, right behind the transposes: see there)
-		for (int i = 0, k = 0; i < ch.a.n_steps && k < 2; ++i)   // the first steps read the heads' (foot-summed) first-layer dZ
-			if (ch.a.step[i].src_kind == FS_SRC_GLOBAL) { ch.a.step[i].src = (k == 0 && act_d) ? (d.shared ? b.zsD : b.dzD[cd]) : (d.shared ? b.zsC : b.dzC[cc]); ++k; }
-		FIND_TRY(launch_chain(c, ch, V, d.feet_t, s, b.w6, chain_w6_bytes(p)));
+		// (the chain was built, and its weights split, right behind the transposes: see there)
+		FIND_TRY(launch_chain(c, tch, V, d.feet_t, s, b.w6, chain_w6_bytes(p)));
 		// the trunk's weight gradients: all their inputs exist now -- one grouped launch + one grouped reduce (fp32), as in the small-call path
-		const bool grouped = grouped_v;
-		for (int l = p->n_trunk - 1; l >= 1; --l) {
-			if (grouped) {
-				FIND_TRY(wgrad_group_add(c, G, b, b.dzT[ct], w.H[l - 1], V * W, d.feet_t, V, g->trunk_w[l], W, g->trunk_b[l], nullptr));
-			} else {
-				const int k = fk.on ? 1 + (l & 1) : 0;
-				BwdWs bk = b;
-				bk.pw = b.pw_t[k]; bk.pb = b.pb_t[k];
-				fk.fork_to(k);
-				FIND_TRY(weight_grad(c, &fk, b.dzT[ct], w.H[l - 1], V * W, nullptr, 0, p, 1, d.feet_t, V, bk, g->trunk_w[l], W, W, 0, g->trunk_b[l], nullptr, fk.stream(k)));
-			}
-			ct += 1;
-		}
-		if (grouped) {
+		for (int l = p->n_trunk - 1; l >= 1; --l, ++ct) FIND_TRY(trunk_wgrad(l, b.dzT[ct]));
+		if (grouped_v) {
 			fk.fork_to(T1);
 			FIND_TRY(wgrad_group_launch(c, G, fk.stream(T1)));
 		}
 	} else {
-	// 4. gradient wrt the trunk output: both heads (and, for a shared trunk, every foot) summed in the K loop
+		// 4. gradient wrt the trunk output: both heads (and, for a shared trunk, every foot) summed in the K loop
 		{
-			GemmArgs a = gemm_args_zero();
+			Gemm2Args a = gemm_args();
 			const float* A[2]; const float* Wt[2]; int nb = 0;
-			if (act_d) { A[nb] = d.shared ? b.zsD : b.dzD[cd]; Wt[nb] = b.Dt[0]; ++nb; }
-			if (act_c) { A[nb] = d.shared ? b.zsC : b.dzC[cc]; Wt[nb] = b.Ct[0]; ++nb; }
-			a.nbase = nb; a.a0 = A[0]; a.w0 = Wt[0];
+			if (act_d) { A[nb] = d.shared ? hd.zs : hd.dz[hd.cur]; Wt[nb] = hd.wt[0]; ++nb; }
+			if (act_c) { A[nb] = d.shared ? hc.zs : hc.dz[hc.cur]; Wt[nb] = hc.wt[0]; ++nb; }
+			a.nseg = nb; a.a0 = A[0]; a.w0 = Wt[0];
 			if (nb > 1) { a.a1 = A[1]; a.w1 = Wt[1]; }
 			a.lda = W; a.ldw = W; a.nchunk = W / KC;
 			a.a_foot_stride = d.shared ? 0 : V * W;  // shared: the foot-summed (V,256) matrices
@@ -1634,31 +1377,21 @@ static int mlp_bwd_body(find_ctx* c, Fork& fk, const find_mlp_params* p, const D
 			FIND_TRY(launch_gemm(c, AMODE_MAT, EPI_MASK, a, d.feet_t, s));
 			FIND_LAUNCH_CHECK("trunk-out dX gemm");
 		}
-
-	// 5. trunk: the dX chain runs back to back on the caller's stream, the layers' weight gradients -- independent of each other,
-		// each filling a fraction of the chip -- alternate between T1 and T2 (own slab set each); Q / set 0 keeps the Fourier layer
-		for (int l = p->n_trunk - 1; l >= 1; --l) {
-			const int k = fk.on ? 1 + (l & 1) : 0;
-			BwdWs bk = b;
-			bk.pw = b.pw_t[k]; bk.pb = b.pb_t[k];
-			fk.fork_to(k);
-			FIND_TRY(weight_grad(c, &fk, b.dzT[ct], w.H[l - 1], V * W, nullptr, 0, p, 1, d.feet_t, V, bk, g->trunk_w[l], W, W, 0, g->trunk_b[l], nullptr, fk.stream(k)));
-			const WT t = wt_T(l);
-			FIND_TRY(linear_bwd_dx(c, b.dzT[ct], t.w, t.ld, t.tr, w.H[l - 1], b.dzT[ct + 1], V, d.feet_t, s));
-			ct += 1;
+		// 5. trunk: the dX chain runs back to back on the caller's stream, the layers' weight gradients beside it; Q / set 0 keeps the Fourier layer
+		for (int l = p->n_trunk - 1; l >= 1; --l, ++ct) {
+			FIND_TRY(trunk_wgrad(l, b.dzT[ct]));
+			FIND_TRY(launch_gemm(c, AMODE_MAT, EPI_MASK, dx_args(b.dzT[ct], wt_T(l), w.H[l - 1], b.dzT[ct + 1], Virt{nullptr, nullptr, 0}), d.feet_t, s));
 		}
 	}
 	if (fused && d.shared && fk.on) {
 		// (round 6: on Q the Fourier layer's weight gradient queued behind the last large layer's dw6 AND its slab reduce -- 60 us after the
 		// trunk's dX chain had produced its input, at the very end of the step; T2 is idle by then, and its slab set is the Fourier layer's size)
 		fk.fork_to(T2);
-		BwdWs bk = b;
-		bk.pw = b.pw_t[T2]; bk.pb = b.pb_t[T2];
-		FIND_TRY(weight_grad(c, &fk, b.dzT[ct], nullptr, 0, pos, V * 3, p, d.nkt0, d.feet_t, V, bk, g->trunk_w[0], K0, 0, 1, g->trunk_b[0], nullptr, fk.stream(T2)));
+		FIND_TRY(fourier_wgrad(b.dzT[ct], T2, T2));
 	} else {
 		fk.fork_to(Q);
 		fk.wait(Q, set_free[0]);
-		FIND_TRY(weight_grad(c, &fk, b.dzT[ct], nullptr, 0, pos, V * 3, p, d.nkt0, d.feet_t, V, b, g->trunk_w[0], K0, 0, 1, g->trunk_b[0], nullptr, fk.stream(Q)));
+		FIND_TRY(fourier_wgrad(b.dzT[ct], Q, 0));
 	}
 	FIND_LAUNCH_CHECK("find_mlp_bwd");
 	return FIND_OK;
@@ -1666,6 +1399,57 @@ static int mlp_bwd_body(find_ctx* c, Fork& fk, const find_mlp_params* p, const D
 
 }  // namespace mlp
 }  // namespace find
+
+// ------------------------------------------------------------------------------------------- entry points
+extern "C" int64_t find_mlp_ws_bytes(const find_mlp_params* p, int64_t pos_batch, int64_t n_feet, int64_t n_pts, int save_for_bwd) {
+	Dims d;
+	if (make_dims(p, pos_batch, n_feet, n_pts, &d) != FIND_OK) return -1;
+	FwdWs w;
+	carve_fwd(p, d, save_for_bwd != 0, nullptr, &w);
+	return w.bytes;
+}
+
+extern "C" int find_mlp_fwd(find_ctx* c, const find_mlp_params* p, const float* pos, int64_t pos_batch, int64_t n_feet, int64_t n_pts,
+							const float* lat_disp, const float* lat_col, float* disp, float* col, void* ws,
+							int64_t ws_bytes, int save_for_bwd, void* stream) {
+	FIND_TRY(check_ctx(c, "find_mlp_fwd"));
+	Dims d;
+	FIND_TRY(make_dims(p, pos_batch, n_feet, n_pts, &d));
+	FIND_TRY(check_weights(p));
+	FIND_REQUIRE(pos && ws, "find_mlp_fwd: pos/ws is NULL");
+	FIND_REQUIRE(disp || col, "find_mlp_fwd: both outputs NULL");
+	// (the latents of a head the call does not evaluate may be NULL: nothing reads them)
+	FIND_REQUIRE(p->lat_disp == 0 ? lat_disp == nullptr : (lat_disp != nullptr || disp == nullptr), "find_mlp_fwd: lat_disp pointer does not match params.lat_disp=%d", p->lat_disp);
+	FIND_REQUIRE(p->lat_col == 0 ? lat_col == nullptr : (lat_col != nullptr || col == nullptr), "find_mlp_fwd: lat_col pointer does not match params.lat_col=%d", p->lat_col);
+	FIND_REQUIRE(p->precision >= 0 && p->precision <= 3, "find_mlp_fwd: params.precision must be 0 (context default), 1 (fp32 MFMA), 2 (fp16) or 3 (bf16x3), got %d", p->precision);
+	FwdWs w;
+	carve_fwd(p, d, save_for_bwd != 0, ws, &w);
+	if (ws_bytes < w.bytes) {
+		set_error("find_mlp_fwd: workspace too small (%lld < %lld)", (long long)ws_bytes, (long long)w.bytes);
+		return FIND_EWORKSPACE;
+	}
+	c->f16 = call_f16(c, p);
+	c->x3 = call_x3(c, p);
+	Fork fk(c, reinterpret_cast<hipStream_t>(stream), c->fwd_streams != 0);
+	Head heads[2];
+	make_heads(heads, p, w, lat_disp, lat_col, nullptr, nullptr);
+	heads[0].out = disp; heads[1].out = col;
+	const int rc = mlp_fwd_body(fk, p, d, w, pos, heads);
+	const int rj = fk.join();   // on every path: the caller may free `ws` right after an error return
+	return rc != FIND_OK ? rc : rj;
+}
+
+extern "C" int find_linear_relu_fwd(find_ctx* c, const float* x, const float* w, const float* b, int64_t n_feet, int64_t n_pts, float* y, void* stream) {
+	FIND_TRY(check_ctx(c, "find_linear_relu_fwd"));
+	FIND_REQUIRE(x && w && b && y, "find_linear_relu_fwd: NULL argument");
+	FIND_REQUIRE(n_feet >= 1 && n_pts >= 1 && n_feet < (1 << 16), "find_linear_relu_fwd: bad sizes");
+	FIND_REQUIRE(aligned16(w) && aligned16(x), "find_linear_relu_fwd: x and w must be 16-byte aligned");
+	c->f16 = c->mlp_f16 == 1;
+	c->x3 = c->mlp_f16 == 2;
+	FIND_TRY(launch_gemm(c, AMODE_MAT, EPI_BIAS_RELU, linear_args(x, n_pts * W, w, W, b, 0, y, n_pts), n_feet, reinterpret_cast<hipStream_t>(stream)));
+	FIND_LAUNCH_CHECK("find_linear_relu_fwd");
+	return FIND_OK;
+}
 
 // Slabs of one weight-gradient launch: up to max(512, feet) + feet + 16 partial 256x256 tiles and as many 256-float bias rows.
 static int64_t wgrad_slabs(int64_t n_feet) { return std::max<int64_t>(512, n_feet) + n_feet + 16; }
@@ -1685,13 +1469,13 @@ extern "C" int find_linear_wgrad(find_ctx* c, const float* dz, const float* x, i
 		set_error("find_linear_wgrad: scratch too small (%lld < %lld)", (long long)scratch_bytes, (long long)find_linear_wgrad_scratch_bytes(n_feet));
 		return FIND_EWORKSPACE;
 	}
-	BwdWs b;
-	memset(&b, 0, sizeof(b));
-	b.pw = static_cast<float*>(scratch);
-	b.pb = b.pw + wgrad_slabs(n_feet) * W * W;
+	float* const pw = static_cast<float*>(scratch);
+	Wgrad wg;
+	wg.dz = dz; wg.x = x; wg.x_foot_stride = n_pts * W; wg.feet = n_feet; wg.V = n_pts; wg.dw = dw; wg.db = db;
+	wg.s = reinterpret_cast<hipStream_t>(stream);
 	c->f16 = c->mlp_f16 == 1;
 	c->x3 = c->mlp_f16 == 2;
-	FIND_TRY(weight_grad(c, nullptr, dz, x, n_pts * W, nullptr, 0, nullptr, 1, n_feet, n_pts, b, dw, W, W, 0, db, nullptr, reinterpret_cast<hipStream_t>(stream)));
+	FIND_TRY(weight_grad(c, nullptr, nullptr, wg, Slabs{pw, pw + wgrad_slabs(n_feet) * W * W}));
 	FIND_LAUNCH_CHECK("find_linear_wgrad");
 	return FIND_OK;
 }
@@ -1747,269 +1531,15 @@ extern "C" int find_mlp_bwd(find_ctx* c, const find_mlp_params* p, const float* 
 	// The caller keeps scratch, workspace and gradient buffers alive until then.  Not under stream capture, not for the large-call paths.
 	const bool defer = c->defer_join != 0 && fk.on && !fk.capturing && !d.shared && use_fused(c, d.V, d.feet_t) && p->pe_size > 0 && g->trunk_w[0] != nullptr;
 	c->defer_join = 0;
-	const int rc = mlp_bwd_body(c, fk, p, d, w, b, pos, lat_disp, lat_col, d_disp, d_col, g, defer);
+	fk.deferring = defer;
+	Head heads[2];
+	make_heads(heads, p, w, lat_disp, lat_col, &b, g);
+	heads[0].gout = d_disp; heads[1].gout = d_col;
+	const int rc = mlp_bwd_body(fk, p, d, w, b, pos, heads, g);
 	// join on EVERY path: the caller's stream continues only after every side stream this call touched has finished, so scratch,
 	// workspace and gradient buffers may be freed (stream-ordered) as soon as the call returns -- also after an error
 	const int rj = (defer && rc == FIND_OK) ? fk.defer() : fk.join();
 	return rc != FIND_OK ? rc : rj;
-}
-
-// Make `stream` wait for the side-stream work an earlier find_mlp_bwd left running ("defer_join").  Returns 1 if there was any, 0 if not.
-extern "C" int find_ctx_join(find_ctx* c, void* stream) {
-	FIND_TRY(check_ctx(c, "find_ctx_join"));
-	int any = 0;
-	for (int k = 0; k < N_SIDE; ++k)
-		if (c->pend[k]) {
-			FIND_HIP_OK(hipStreamWaitEvent(reinterpret_cast<hipStream_t>(stream), c->pend_ev[k], 0), "hipStreamWaitEvent");
-			c->pend[k] = false;
-			any = 1;
-		}
-	return any ? 1 : FIND_OK;
-}
-
-// ------------------------------------------------------------------------------------------- streams and hardware queues
-// HIP multiplexes streams onto a few hardware queues (GPU_MAX_HW_QUEUES, four by default), in creation order; two streams on one queue
-// run their launches in order.  Which of the context's side streams really run beside the caller's stream -- and beside each other --
-// therefore depends on what the process created before: a probe launch tells.
-namespace find {
-namespace mlp {
-__global__ void spin_kernel(long long ticks) {
-	const long long t0 = wall_clock64();   // 100 MHz
-	while (wall_clock64() - t0 < ticks) __builtin_amdgcn_s_sleep(64);
-}
-__global__ void nop_kernel() {}
-}  // namespace mlp
-}  // namespace find
-
-// does a launch on b run while a is busy?  "Yes" cannot be wrong (on one queue b's launch cannot finish before a's spin); "no" can, when
-// the host thread is held up between b's completion and the query for longer than the spin: a "no" is asked again, twice.
-static int runs_beside(hipStream_t a, hipStream_t b, hipEvent_t ea, hipEvent_t eb, bool* beside) {
-	*beside = false;
-	for (int attempt = 0; attempt < 3 && !*beside; ++attempt) {
-		FIND_HIP_OK(hipStreamSynchronize(a), "hipStreamSynchronize");
-		FIND_HIP_OK(hipStreamSynchronize(b), "hipStreamSynchronize");
-		hipLaunchKernelGGL(find::mlp::spin_kernel, dim3(1), dim3(64), 0, a, 30000ll << attempt);   // ~0.3 ms, then 0.6, 1.2
-		FIND_HIP_OK(hipEventRecord(ea, a), "hipEventRecord");
-		hipLaunchKernelGGL(find::mlp::nop_kernel, dim3(1), dim3(64), 0, b);
-		FIND_HIP_OK(hipEventRecord(eb, b), "hipEventRecord");
-		FIND_HIP_OK(hipEventSynchronize(eb), "hipEventSynchronize");
-		*beside = hipEventQuery(ea) == hipErrorNotReady;
-		FIND_HIP_OK(hipStreamSynchronize(a), "hipStreamSynchronize");
-	}
-	return FIND_OK;
-}
-
-// groups[0] = 0 for the caller's stream, groups[1 + k] for side stream k: streams with the same number share a hardware queue
-static int stream_groups(hipStream_t const* st, int n, hipEvent_t ea, hipEvent_t eb, int* groups) {
-	int ngroups = 0;
-	int rep[16];
-	for (int i = 0; i < n; ++i) {
-		groups[i] = -1;
-		for (int g = 0; g < ngroups && groups[i] < 0; ++g) {
-			bool beside = false;
-			FIND_TRY(runs_beside(st[rep[g]], st[i], ea, eb, &beside));
-			if (!beside) groups[i] = g;
-		}
-		if (groups[i] < 0) {
-			if (ngroups == 16) { groups[i] = 15; continue; }
-			rep[ngroups] = i;
-			groups[i] = ngroups++;
-		}
-	}
-	return FIND_OK;
-}
-
-extern "C" int find_ctx_stream_groups(find_ctx* c, void* caller_stream, int32_t* groups) {
-	FIND_TRY(check_ctx(c, "find_ctx_stream_groups"));
-	FIND_REQUIRE(groups != nullptr, "find_ctx_stream_groups: groups is NULL");
-	hipStream_t st[1 + N_SIDE];
-	st[0] = reinterpret_cast<hipStream_t>(caller_stream);
-	for (int k = 0; k < N_SIDE; ++k) st[1 + k] = c->side[k];
-	int g[1 + N_SIDE];
-	FIND_TRY(stream_groups(st, 1 + N_SIDE, c->ev[0], c->ev[1], g));
-	for (int k = 0; k < 1 + N_SIDE; ++k) groups[k] = g[k];
-	return FIND_OK;
-}
-
-namespace find { namespace mlp { static int bind_side_streams(find_ctx* c, hipStream_t caller); } }
-
-// A caller's second stream that fits the context's layout: the first of `cands` that runs BESIDE caller_stream and shares the hardware queue
-// of side stream `role` (0 = Q: the large head layers' weight gradients -- busy only during the main pass's backward).  With four hardware
-// queues a fifth stream always shares one; which one decides what its work waits behind (find_hip.h).  *index = -1: none of them does.
-extern "C" int find_ctx_stream_beside(find_ctx* c, void* caller_stream, void* const* cands, int32_t n, int32_t role, int32_t* index) {
-	FIND_TRY(check_ctx(c, "find_ctx_stream_beside"));
-	FIND_REQUIRE(cands != nullptr && index != nullptr && n >= 0 && role >= 0 && role < N_SIDE, "find_ctx_stream_beside: bad arguments (role 0..%d)", N_SIDE - 1);
-	hipStream_t caller = reinterpret_cast<hipStream_t>(caller_stream);
-	if (!c->side_bound && c->bind_streams) (void)find::mlp::bind_side_streams(c, caller);
-	*index = -1;
-	for (int i = 0; i < n; ++i) {
-		hipStream_t s = reinterpret_cast<hipStream_t>(cands[i]);
-		bool beside_caller = false, beside_role = true;
-		FIND_TRY(runs_beside(caller, s, c->ev[0], c->ev[1], &beside_caller));
-		if (!beside_caller) continue;
-		FIND_TRY(runs_beside(c->side[role], s, c->ev[0], c->ev[1], &beside_role));
-		if (!beside_role) { *index = i; break; }
-	}
-	return FIND_OK;
-}
-
-// The layout the step was tuned with (and gets in a process that creates nothing else first): the large weight gradients (Q) and the two
-// small-launch streams (T1, T2) each on a queue of their own, none of them the caller's, and the slab reduces (R) behind T2's queue.
-// After torch.distributed has created RCCL's streams the same four hipStreamCreate calls put R on the CALLER's queue -- the reduces then
-// sit between the dX GEMMs: 3.47 instead of 3.25 ms per train_3d step on every rank of a multi-GPU run.  So the first call that forks
-// chooses its side streams among a dozen candidates by probing (once per context, ~20 ms).
-namespace find {
-namespace mlp {
-static int bind_side_streams(find_ctx* c, hipStream_t caller) {
-	c->side_bound = true;   // (one attempt: a failure below keeps the streams as created)
-	constexpr int N_CAND = 12;
-	hipStream_t st[1 + N_CAND];
-	st[0] = caller;
-	int n = 1;
-	for (int k = 0; k < N_SIDE; ++k) st[n++] = c->side[k];
-	for (; n < 1 + N_CAND; ++n)
-		if (hipStreamCreateWithFlags(&st[n], hipStreamNonBlocking) != hipSuccess) break;
-	int g[1 + N_CAND];
-	int rc = stream_groups(st, n, c->ev[0], c->ev[1], g);
-	int pick[N_SIDE] = {-1, -1, -1, -1};
-	if (rc == FIND_OK) {
-		int ng = 0;
-		for (int k = 0; k < 3; ++k)   // Q, T1, T2: first candidate on a queue that is neither the caller's nor an earlier pick's
-			for (int i = 1; i < n && pick[k] < 0; ++i) {
-				bool fresh = g[i] != 0;
-				for (int j = 0; j < k; ++j) fresh = fresh && g[i] != g[pick[j]];
-				if (fresh) { pick[k] = i; ++ng; }
-			}
-		if (ng == 3) {
-			for (int i = 1; i < n && pick[3] < 0; ++i)   // R: another stream on T2's queue
-				if (i != pick[0] && i != pick[1] && i != pick[2] && g[i] == g[pick[2]]) pick[3] = i;
-			if (pick[3] < 0)   // (none: any stream that is not on the caller's queue and not a pick)
-				for (int i = 1; i < n && pick[3] < 0; ++i)
-					if (g[i] != 0 && i != pick[0] && i != pick[1] && i != pick[2]) pick[3] = i;
-		}
-	}
-	const bool ok = rc == FIND_OK && pick[0] > 0 && pick[1] > 0 && pick[2] > 0 && pick[3] > 0;
-	hipStream_t chosen[N_SIDE];
-	for (int k = 0; k < N_SIDE; ++k) chosen[k] = ok ? st[pick[k]] : c->side[k];
-	for (int i = 1; i < n; ++i) {
-		bool keep = false;
-		for (int k = 0; k < N_SIDE; ++k) keep = keep || st[i] == chosen[k];
-		if (!keep) (void)hipStreamDestroy(st[i]);
-	}
-	for (int k = 0; k < N_SIDE; ++k) c->side[k] = chosen[k];
-	return rc;
-}
-}  // namespace mlp
-}  // namespace find
-
-// ------------------------------------------------------------------------------------------- context
-extern "C" int find_ctx_create(int device, find_ctx** out) {
-	FIND_REQUIRE(out != nullptr, "find_ctx_create: out is NULL");
-	*out = nullptr;
-	int prev = 0, ndev = 0;
-	FIND_HIP_OK(hipGetDeviceCount(&ndev), "hipGetDeviceCount");
-	FIND_REQUIRE(device >= 0 && device < ndev, "find_ctx_create: device %d out of range (%d visible)", device, ndev);
-	FIND_HIP_OK(hipGetDevice(&prev), "hipGetDevice");
-	FIND_HIP_OK(hipSetDevice(device), "hipSetDevice");
-	find_ctx* c = new find_ctx();
-	c->device = device;
-	auto fail = [&](const char* what, hipError_t e) {
-		set_error("find_ctx_create: %s: %s", what, hipGetErrorString(e));
-		for (int i = 0; i < c->n_events; ++i) (void)hipEventDestroy(c->ev[i]);
-		for (int i = 0; i < N_SIDE; ++i) if (c->side[i]) (void)hipStreamDestroy(c->side[i]);
-		delete c;
-		(void)hipSetDevice(prev);
-		return FIND_ELAUNCH;
-	};
-	hipError_t e;
-	int v = 0;
-	if ((e = hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, device)) != hipSuccess) return fail("CU count", e);
-	c->num_cus = v > 0 ? v : 256;
-	if ((e = hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, device)) != hipSuccess) return fail("LDS size", e);
-	c->lds_bytes = v;
-	for (int i = 0; i < N_SIDE; ++i)
-		if ((e = hipStreamCreateWithFlags(&c->side[i], hipStreamNonBlocking)) != hipSuccess) return fail("hipStreamCreateWithFlags", e);
-	for (c->n_events = 0; c->n_events < N_EVENTS; ++c->n_events)
-		if ((e = hipEventCreateWithFlags(&c->ev[c->n_events], hipEventDisableTiming)) != hipSuccess) return fail("hipEventCreateWithFlags", e);
-	for (int i = 0; i < N_SIDE; ++i)
-		if ((e = hipEventCreateWithFlags(&c->pend_ev[i], hipEventDisableTiming)) != hipSuccess) return fail("hipEventCreateWithFlags", e);
-	FIND_HIP_OK(hipSetDevice(prev), "hipSetDevice");
-	*out = c;
-	return FIND_OK;
-}
-
-extern "C" int find_ctx_destroy(find_ctx* c) {
-	if (!c) return FIND_OK;
-	int prev = 0;
-	(void)hipGetDevice(&prev);
-	(void)hipSetDevice(c->device);
-	for (int i = 0; i < N_SIDE; ++i) if (c->side[i]) (void)hipStreamDestroy(c->side[i]);
-	for (int i = 0; i < c->n_events; ++i) (void)hipEventDestroy(c->ev[i]);
-	(void)hipSetDevice(prev);
-	delete c;
-	return FIND_OK;
-}
-
-namespace {
-struct Knob { const char* key; int find_ctx::*field; int64_t lo, hi; };
-const Knob KNOBS[] = {
-	{"gemm4_small", &find_ctx::gemm4_small, 0, INT32_MAX},
-	{"gemm5_min_units", &find_ctx::gemm5_min_units, 0, INT32_MAX},
-	{"gemm6_min_units", &find_ctx::gemm6_min_units, 0, INT32_MAX},
-	{"mlp_f16", &find_ctx::mlp_f16, 0, 2},
-	{"fused_max_units", &find_ctx::fused_max_units, 0, 1024},
-	{"fused6", &find_ctx::fused6, 0, 1},
-	{"dw2_min_cps", &find_ctx::dw2_min_cps, 1, INT32_MAX},
-	{"dw_lds_free", &find_ctx::dw_lds_free, 0, 1},
-	{"lds_exclusive", &find_ctx::lds_exclusive, 0, 1},
-	{"reduce_exclusive", &find_ctx::reduce_exclusive, 0, 2},
-	{"bwd_streams", &find_ctx::bwd_streams, 0, 1},
-	{"fwd_streams", &find_ctx::fwd_streams, 0, 1},
-	{"reduce_stream", &find_ctx::reduce_stream, 0, 1},
-	{"bind_streams", &find_ctx::bind_streams, 0, 1},
-	{"defer_join", &find_ctx::defer_join, 0, 1},
-	{"act16", &find_ctx::act16, 0, 1},
-	{"bcast_fold", &find_ctx::bcast_fold, 0, 1},
-	{"footsum_fold", &find_ctx::footsum_fold, 0, 1},
-};
-}  // namespace
-
-extern "C" int find_ctx_set(find_ctx* c, const char* key, int64_t value) {
-	FIND_REQUIRE(c != nullptr && key != nullptr, "find_ctx_set: NULL argument");
-	if (strcmp(key, "ablate") == 0) {
-		FIND_REQUIRE(value >= 0 && value <= INT32_MAX && (value & ~(int64_t)find::MLP_SWITCHES) == 0,
-		             "find_ctx_set: ablate = %lld has bits outside the result-preserving switches 0x%x", (long long)value, find::MLP_SWITCHES);
-		c->ablate = (int)value;
-		return FIND_OK;
-	}
-	if (strcmp(key, "gemm4_min_units") == 0) {
-		FIND_REQUIRE(value >= 0, "find_ctx_set: gemm4_min_units must be >= 0");
-		c->gemm4_min_units = value;
-		return FIND_OK;
-	}
-	for (const Knob& k : KNOBS)
-		if (strcmp(key, k.key) == 0) {
-			FIND_REQUIRE(value >= k.lo && value <= k.hi, "find_ctx_set: %s = %lld out of range [%lld, %lld]", key, (long long)value, (long long)k.lo, (long long)k.hi);
-			c->*(k.field) = (int)value;
-			return FIND_OK;
-		}
-	set_error("find_ctx_set: unknown key %s", key);
-	return FIND_EINVAL;
-}
-
-extern "C" int find_ctx_get(const find_ctx* c, const char* key, int64_t* value) {
-	FIND_REQUIRE(c != nullptr && key != nullptr && value != nullptr, "find_ctx_get: NULL argument");
-	if (strcmp(key, "num_cus") == 0) { *value = c->num_cus; return FIND_OK; }
-	if (strcmp(key, "pending") == 0) { *value = (c->pend[0] || c->pend[1] || c->pend[2] || c->pend[3]) ? 1 : 0; return FIND_OK; }
-	if (strcmp(key, "lds_bytes") == 0) { *value = c->lds_bytes; return FIND_OK; }
-	if (strcmp(key, "device") == 0) { *value = c->device; return FIND_OK; }
-	if (strcmp(key, "events_per_call_max") == 0) { *value = c->events_per_call_max; return FIND_OK; }
-	if (strcmp(key, "gemm4_min_units") == 0) { *value = c->gemm4_min_units; return FIND_OK; }
-	if (strcmp(key, "ablate") == 0) { *value = c->ablate; return FIND_OK; }
-	for (const Knob& k : KNOBS)
-		if (strcmp(key, k.key) == 0) { *value = c->*(k.field); return FIND_OK; }
-	set_error("find_ctx_get: unknown key %s", key);
-	return FIND_EINVAL;
 }
 
 extern "C" int find_render_switches(int64_t bits) {

@@ -60,47 +60,6 @@ __host__ __device__ __forceinline__ int pe_col_to_orig(int kp, int pe, int in_di
 	return q < in_dim ? q : -1;
 }
 
-// ---------------------------------------------------------------------------------------------
-// GEMM  Y[(foot,v), n] = epi( sum_seg sum_k A_seg[(foot,v), k] * Wseg[n, k] ),  n in [0,256)
-// Used for every forward Linear (EPI_BIAS_RELU) and every backward dX (EPI_MASK, W pre-transposed).
-// Segments let the backward sum the contributions of both heads and -- when the trunk is shared by
-// all feet -- of every foot, inside the K loop (deterministic, no atomics).
-// ---------------------------------------------------------------------------------------------
-struct GemmArgs {
-	const float* a0;  // A base for segments [0, nseg_per_base)
-	const float* a1;  // A base for segments [nseg_per_base, 2*nseg_per_base) (nbase == 2)
-	int nbase;
-	int nseg_per_base;
-	int64_t a_seg_stride;   // elements between consecutive segments of one base
-	int64_t a_foot_stride;  // elements between feet (blockIdx.y); 0 = rows shared by all feet
-	int lda;
-	const float* pos;       // AMODE_PE: (pos_batch, V, 3)
-	int64_t pos_foot_stride;
-	const float* Bm;        // AMODE_PE: (3, pe)
-	int pe;
-	const float* w0;        // (256, ldw), K contiguous
-	const float* w1;
-	int ldw;
-	int w_tr;               // host side (launch_gemm): w0 is untransposed and the launch goes to gemm7, which reads it transposed (linear_bwd_dx)
-	int nchunk;             // 32-wide K chunks per segment
-	const float* bias;      // EPI_BIAS_RELU: (.., 256)
-	int64_t bias_foot_stride;
-	const float* mask;      // EPI_MASK: same layout as y; output zeroed where mask <= 0
-	int64_t mask_foot_stride;
-	float* y;
-	int64_t y_foot_stride;
-	int ldy;
-	int V;                  // rows per foot
-	int h16;                // host side only (launch_gemm): a0, y and mask are fp16-STORED tensors (act16: gemm5_kernel<EPI, true>)
-	const float* va_bias;   // bcast_fold: a0 is the shared fp32 product P and the operand is relu(P[v] + va_bias[foot]) (gemm5_kernel<.., VIRT>)
-	int64_t va_bias_stride;
-	const float* vm_bias;   // bcast_fold: mask is P and the mask is P[v] + vm_bias[foot]
-	int64_t vm_bias_stride;
-	float* fs_out;          // footsum_fold (with vm_bias): no y; the sum over feet goes to fs_out (+ fs_slot_stride: second partial), the per-foot
-	int64_t fs_slot_stride; // column sums to cs_out [workgroup pair][foot][256] (gemm7_kernel<.., FSUM>)
-	float* cs_out;
-};
-
 enum { AMODE_MAT = 0, AMODE_PE = 1 };
 enum { EPI_NONE = 0, EPI_BIAS_RELU = 1, EPI_MASK = 2 };
 
