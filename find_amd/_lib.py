@@ -119,6 +119,7 @@ PROTOTYPES = {
 	'find_render_features_fwd': (c_int, [POINTER(RenderParams), _P, _P, _I, _P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _I, _P, _I, _P]),
 	'find_render_features_bwd': (c_int, [POINTER(RenderParams), _P, _P, _I, _P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _I, _P, _I, _P]),
 	'find_points_render': (c_int, [POINTER(PointsParams), _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
+	'find_frames_u8': (c_int, [_P, _I, _I, _I, _I, c_int, _P, _P]),
 }
 
 

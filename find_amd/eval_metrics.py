@@ -1,7 +1,7 @@
 """Metric definitions of reference src/eval/eval_3d.py on the HIP path (row a16): keypoint error in mm (eval_3d.py:142,
 220-221), Chamfer over 10 000 surface samples reported x1e6 as "um" (eval_3d.py:148-151, 223 -- the reference's
 scaling of a m^2 quantity is kept) and the per-foot z <= 0.07 cut-off variant (eval_3d.py:154-161).
-Tables, plots, spins and OBJ export of the eval script are out of scope.
+Spins, heat maps and OBJ export of the eval script: find_amd.vis / find_amd.evaluate.eval_3d; its tables and plots are out of scope.
 
 The 2-D half: MSE, PSNR, MSE_masked, PSNR_masked and IOU under the names and semantics of reference src/eval/eval_metrics.py (so that
 `from find_amd.eval_metrics import IOU, MSE, PSNR, MSE_masked, PSNR_masked` replaces that import), and eval_2d_metrics, the per-group
@@ -26,8 +26,10 @@ def keypoint_error_mm(pred_verts, template_kp_idxs, gt_kps):
 
 
 def eval_3d_metrics(pred_meshes, gt_meshes, pred_verts=None, template_kp_idxs=None, gt_kps=None, samples=10000, z_cutoff=0.07,
-					draws_gt=None, draws_pred=None):
-	"""Returns {'Keypoint (mm)', 'Chamf z-cutoff <z> (um)', 'Chamf (um)'} as 0-d tensors (keypoints only when given)."""
+					draws_gt=None, draws_pred=None, return_samples=False):
+	"""Returns {'Keypoint (mm)', 'Chamf z-cutoff <z> (um)', 'Chamf (um)'} as 0-d tensors (keypoints only when given); with return_samples
+	also (gt_pts, pred_pts), the (N,samples,3) surface samples the Chamfer terms were taken on (the per-vertex heat maps of eval_3d.py:171-178
+	read the predicted ones: no second draw)."""
 	with torch.no_grad():
 		gt_pts = sample_points_from_meshes(gt_meshes, num_samples=samples, draws=draws_gt)
 		pred_pts = sample_points_from_meshes(pred_meshes, num_samples=samples, draws=draws_pred)
@@ -44,7 +46,7 @@ def eval_3d_metrics(pred_meshes, gt_meshes, pred_verts=None, template_kp_idxs=No
 		out = {f'Chamf z-cutoff {z_cutoff} (μm)': chamf_cut * 1e6, 'Chamf (μm)': chamf * 1e6}
 		if template_kp_idxs is not None:
 			out['Keypoint (mm)'] = keypoint_error_mm(pred_verts, template_kp_idxs, gt_kps)
-	return out
+	return (out, (gt_pts, pred_pts)) if return_samples else out
 
 
 # ---------------------------------------------------------------------------------------------- 2-D (eval_2d.py, eval_metrics.py)

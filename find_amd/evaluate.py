@@ -5,15 +5,18 @@ and out of scope.
 
 eval_3d is the loop of reference src/eval/eval_3d.py (main, eval_3d.py:56-225) the same way: keypoint error, Chamfer and its z cut-off
 variant (eval_metrics.eval_3d_metrics) over every validation foot, and optionally the per-foot keypoint table behind errors.png and the
-top-down keypoint renders of render_correspondences (eval_3d.py:94-99).  PNG / mp4 / OBJ writes, spins, per-vertex error textures and the
-matplotlib table are out of scope."""
+top-down keypoint renders of render_correspondences (eval_3d.py:94-99); with produce_spins / export_meshes the six turntable spins per
+foot with their per-vertex Chamfer heat maps (eval_3d.py:163-201) and the OBJ files (eval_3d.py:204-217), through find_amd.vis.  The PNG
+writes and the matplotlib table are out of scope."""
+import os
+
 import torch
 from torch.utils.data import DataLoader
 
 from .dataset import BatchCollator
 from .eval_metrics import eval_2d_metrics, eval_3d_metrics
 from .renderer import FootRenderer
-from .structures import Meshes
+from .structures import Meshes, TexturesVertex
 
 METRICS = ('MSE', 'PSNR_A', 'PSNR_B', 'PSNR_C', 'IOU')
 
@@ -65,7 +68,8 @@ def eval_2d(model, dataset, image_size=128, nviews=1, batch_size=1, R=None, T=No
 
 
 def eval_3d(model, dataset, template_kp_idxs, samples=10000, z_cutoff=0.07, feet_per_call=16, render_correspondences=False, image_size=256,
-			return_per_foot=False, device='cuda'):
+			return_per_foot=False, device='cuda', produce_spins=False, export_meshes=False, out_dir=None, spin_frames=250, spin_image_size=512,
+			spin_format='gif'):
 	"""model: a NeuralDisplacementField or a PCAModel whose validation latent tables are indexed by the dataset's item index (batch['idx']);
 	dataset: the validation Foot3DDataset, every foot with keypoints; template_kp_idxs: the template vertices of the keypoints (the
 	template foot's kp_idxs for a neural model, eval_metrics.PCA_KEYPOINTS for a PCAModel; eval_3d.py:132-138).  Ground-truth keypoints
@@ -74,7 +78,19 @@ def eval_3d(model, dataset, template_kp_idxs, samples=10000, z_cutoff=0.07, feet
 	on that choice and the Chamfer terms draw their samples as one eval_3d_metrics call over all feet would.
 	Returns {'Keypoint (mm)', 'Chamf z-cutoff <z> (μm)', 'Chamf (μm)'} as floats; with return_per_foot or render_correspondences a second
 	dict follows, holding 'keypoint_mm' (N,K) float32 (the data of errors.png) and / or 'gt' and 'pred', the keypoint_blend images
-	(N,1,H,W,3) from view_from('topdown').  A foot without keypoints raises ValueError (upstream reads vertex 0 for it)."""
+	(N,1,H,W,3) from view_from('topdown').  A foot without keypoints raises ValueError (upstream reads vertex 0 for it).
+	export_meshes writes {out_dir}/meshes/{n:02d}_gt_mesh.obj and {n:02d}_pred_mesh.obj (vis.export_obj: the prediction with its vertex
+	colours, the scan's geometry).  produce_spins writes, per foot n, {out_dir}/spins/{n:02d}_{pred_rgb, pred_chamf, pred_grey, gt_rgb, gt_chamf,
+	gt_grey}.<spin_format>: vis.turntable(azim=70, dist=0.35) of spin_frames frames at spin_image_size, in the mesh's own texture, as the
+	per-vertex heat map vis.error_colours(vis.vertex_errors(...)) -- the GT one against the very predicted samples the Chamfer number was
+	taken on -- and in grey (TexturesVertex(0.5)); each spin is written as it is made.  spin_format: an extension vis.turntable writes
+	('gif', 'png', 'webp', 'npy'; 'mp4' with imageio -- upstream's format).  Either adds to the second dict 'files', the paths written, and
+	produce_spins also 'pred_vertex_error' (N,V) and 'gt_vertex_error', a list of (Vg,) tensors (squared distances).  The metrics do not
+	depend on these keywords: no random number is drawn for them."""
+	if (produce_spins or export_meshes) and out_dir is None:
+		raise ValueError('find_amd.evaluate.eval_3d: produce_spins / export_meshes need out_dir')
+	keep_meshes = produce_spins or export_meshes
+	gt_meshes, pred_meshes = [], []
 	collate = BatchCollator(device=device).collate_batches
 	loader = DataLoader(dataset, batch_size=feet_per_call, shuffle=False, collate_fn=collate)
 	kp_t = torch.as_tensor(template_kp_idxs, dtype=torch.long, device=device)
@@ -100,22 +116,65 @@ def eval_3d(model, dataset, template_kp_idxs, samples=10000, z_cutoff=0.07, feet
 				pred_v += res['meshes'].verts_list(); pred_f += res['meshes'].faces_list()
 				gt_kps.append(gkp)
 				pred_verts.append(res['verts'])
+				if keep_meshes:
+					gt_meshes += [gt[i] for i in range(len(gt))]
+					pred_meshes += [res['meshes'][i] for i in range(len(gt))]
 				if render_correspondences:
 					images['gt'].append(renderer(gt, R, T, return_images=True, keypoints=gkp, keypoints_blend=True)['keypoints_blend'])
 					images['pred'].append(renderer(res['meshes'], R, T, return_images=True, keypoints=pkp, keypoints_blend=True)['keypoints_blend'])
 			gt_kps = torch.cat(gt_kps)
 			pred_verts = torch.cat(pred_verts)
-			metrics = eval_3d_metrics(Meshes(pred_v, pred_f), Meshes(gt_v, gt_f), pred_verts=pred_verts, template_kp_idxs=kp_t, gt_kps=gt_kps,
-									  samples=samples, z_cutoff=z_cutoff)
+			gt_all = Meshes(gt_v, gt_f)
+			metrics, (_, pred_pts) = eval_3d_metrics(Meshes(pred_v, pred_f), gt_all, pred_verts=pred_verts, template_kp_idxs=kp_t, gt_kps=gt_kps,
+													 samples=samples, z_cutoff=z_cutoff, return_samples=True)
 			per_foot = torch.norm(pred_verts[:, kp_t] - gt_kps, dim=-1) * 1e3
+			written = {}
+			if produce_spins:
+				written = _spins(gt_meshes, pred_meshes, gt_all, pred_verts, pred_pts, os.path.join(out_dir, 'spins'), spin_frames, spin_image_size, spin_format)
+			if export_meshes:
+				written.setdefault('files', []).extend(_export(gt_meshes, pred_meshes, os.path.join(out_dir, 'meshes')))
 	finally:
 		model.train(was_training)
 	out = {k: float(metrics[k]) for k in ('Keypoint (mm)', f'Chamf z-cutoff {z_cutoff} (μm)', 'Chamf (μm)')}
-	if not (return_per_foot or render_correspondences):
+	if not (return_per_foot or render_correspondences or keep_meshes):
 		return out
-	extra = {}
+	extra = dict(written)
 	if return_per_foot:
 		extra['keypoint_mm'] = per_foot
 	if render_correspondences:
 		extra.update({k: torch.cat(v) for k, v in images.items()})
 	return out, extra
+
+
+def _spins(gt_meshes, pred_meshes, gt_all, pred_verts, pred_pts, spins_dir, nframes, image_size, fmt):
+	"""The six spins per foot of eval_3d.py:163-201; the heat maps of all feet come from one vertex_errors call.  Returns the error tensors and
+	the files written."""
+	from . import vis
+	os.makedirs(spins_dir, exist_ok=True)
+	n_gt = gt_all.num_verts_per_mesh()
+	pred_err, gt_err = vis.vertex_errors(pred_verts, gt_all.verts_padded(), pred_pts, n_gt)
+	pred_col, gt_col = vis.error_colours(pred_err), vis.error_colours(gt_err)
+	files = []
+	for n, (gt, pred) in enumerate(zip(gt_meshes, pred_meshes)):
+		vg = gt.verts_padded().shape[1]   # (padded to the largest scan of its batch: the rows past its own vertices are in no face)
+		heat_p, heat_g = pred_col[n:n + 1], gt_col[n:n + 1, :vg].contiguous()
+		renders = ((pred, pred.textures, 'pred_rgb'), (pred, TexturesVertex(heat_p), 'pred_chamf'), (pred, TexturesVertex(torch.full_like(heat_p, 0.5)), 'pred_grey'),
+				   (gt, gt.textures, 'gt_rgb'), (gt, TexturesVertex(heat_g), 'gt_chamf'), (gt, TexturesVertex(torch.full_like(heat_g, 0.5)), 'gt_grey'))
+		for mesh, texture, name in renders:
+			mesh = mesh.update_padded(mesh.verts_padded())   # (a shallow copy: the caller's mesh keeps its texture)
+			mesh.textures = texture
+			loc = os.path.join(spins_dir, f'{n:02d}_{name}.{fmt.lstrip(".")}')
+			vis.turntable(mesh, out_loc=loc, nframes=nframes, silent=True, azim=70, dist=0.35, image_size=image_size)
+			files.append(loc)
+	return {'pred_vertex_error': pred_err, 'gt_vertex_error': [gt_err[n, :int(v)] for n, v in enumerate(n_gt)], 'files': files}
+
+
+def _export(gt_meshes, pred_meshes, mesh_dir):
+	"""{n:02d}_gt_mesh.obj and {n:02d}_pred_mesh.obj per foot (eval_3d.py:204-217).  Returns the files written."""
+	from . import vis
+	os.makedirs(mesh_dir, exist_ok=True)
+	files = []
+	for n, (gt, pred) in enumerate(zip(gt_meshes, pred_meshes)):
+		for key, mesh in (('gt_mesh', gt), ('pred_mesh', pred)):
+			files.append(vis.export_obj(mesh, os.path.join(mesh_dir, f'{n:02d}_{key}.obj')))
+	return files

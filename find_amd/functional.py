@@ -1014,6 +1014,29 @@ def image_metric_sums(pred, gt, pred_mask=None, gt_mask=None, hide=None, weight=
 	return sums
 
 
+def frames_u8(images, rot180=True, out=None):
+	"""Video frames of a render: images (..., H, W, C) fp32 -> uint8 of the same shape, (255 * image).astype(np.uint8) -- truncation toward
+	zero, clamped to [0, 255], NaN -> 0 -- and with rot180 every image turned by 180 degrees (cv2.rotate(..., ROTATE_180)), in one pass
+	(find_frames_u8; reference mesh_turntable.py:60-61).  out: a contiguous uint8 tensor of the images' shape on their device to write into
+	(a slice of a spin's frames) instead of a new one.  No gradient, no host synchronisation: runs on the current stream."""
+	if images.dim() < 3:
+		raise ValueError(f'find_amd.frames_u8: images are (..., H, W, C), got {tuple(images.shape)}')
+	_require_gpu(images)
+	if images.dtype != torch.float32:
+		raise RuntimeError(f'find_amd: fp32 tensors required, got {images.dtype}')
+	H, W, C = (int(d) for d in images.shape[-3:])
+	if out is None:
+		out = torch.empty(images.shape, dtype=torch.uint8, device=images.device)
+	elif out.dtype != torch.uint8 or out.shape != images.shape or out.device != images.device or not out.is_contiguous():
+		raise ValueError(f'find_amd.frames_u8: out must be a contiguous uint8 tensor {tuple(images.shape)} on {images.device}, got {out.dtype} {tuple(out.shape)} on {out.device}')
+	if images.numel() == 0:
+		return out
+	images = images.detach().contiguous()   # (held in a local until the launch is queued)
+	check(_lib.lib().find_frames_u8(ptr(images), images.numel() // (H * W * C), H, W, C, int(bool(rot180)), ptr(out), current_stream(images.device)),
+		  'find_frames_u8')
+	return out
+
+
 class MeshTopology:
 	"""Static per-template tables for the smoothness kernels: unique undirected edges, vertex->incident-corner CSR and
 	vertex->neighbour CSR (host-built once, cached per faces tensor)."""

@@ -504,6 +504,15 @@ typedef struct find_points_params {
 int find_points_render(const find_points_params* pp, const float* points, const float* features, const float* R, const float* T,
 					   int64_t n_clouds, int64_t n_views, int64_t P, float* image, int32_t* idx, float* zbuf, float* dists, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Video frames of a render (src/vis/mesh_turntable.py:60-61: (255 * image).astype(np.uint8), then cv2.rotate(..., ROTATE_180)).
+ * img (n,h,w,c) fp32 -> out (n,h,w,c) bytes: out = (uint8) min(max(255.f * x, 0.f), 255.f), i.e. truncation toward zero, NaN -> 0;
+ * with rot180 != 0 pixel (y, x) of image i goes to (h-1-y, w-1-x), channels in order.  1 <= c <= 16, n*h*w*c <= 2^40; img and out must
+ * not overlap.  One pass, no workspace, no host synchronisation; 16-byte loads and packed 32-bit stores when h*w (n*h*w without rot180)
+ * is a multiple of 4, c is 1 or 3 and img / out are 16- / 4-byte aligned, a pixel per thread otherwise.
+ * ---------------------------------------------------------------------------------------------- */
+int find_frames_u8(const float* img, int64_t n, int64_t h, int64_t w, int64_t c, int rot180, uint8_t* out, void* stream);
+
 
 /* ------------------------------------------------------------------------------------------------
  * UV textures.  Replaces pytorch3d TexturesUV.sample_textures as the reference uses it for GT scans
