@@ -7,7 +7,7 @@ from ctypes import POINTER, Structure, c_char_p, c_float, c_int, c_int16, c_int3
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, 'lib', 'libfind_hip.so')
 MAX_LAYERS = 8
-ABI_VERSION = 2
+ABI_VERSION = 3
 
 _lib = None
 
@@ -77,6 +77,9 @@ PROTOTYPES = {
 	'find_weighted_terms_bwd': (c_int, [_I, _P, _P, _P, _P, _P]),
 	'find_contrastive_fwd': (c_int, [_P, _I, _I, _P, _I, _P, _I, c_float, _P, _P, _P]),
 	'find_contrastive_bwd': (c_int, [_P, _I, _I, _P, _I, _P, _P, _P, _P]),
+	'find_part_labels': (c_int, [_P, _I, _I, _I, _I, _I, _I, _P, _P]),
+	'find_part_ce_fwd': (c_int, [_P, _P, _P, _I, _I, _P, _P, _P, _I, _P]),
+	'find_part_ce_bwd': (c_int, [_P, _P, _P, _I, _I, _P, _P, _P, _I, _P]),
 	'find_uv_sample': (c_int, [_P, _I, _I, _I, _P, _I, _P, _I, _I, _P, _P, _I, _I, _P, _P]),
 	'find_render_frags': (c_int, [POINTER(RenderParams), _I, _I, _I, _I, _P, _P, _P, _P]),
 	'find_adam_step': (c_int, [_I, _P, _P, _P, _P, _P, c_float, c_float, c_float, c_float, c_float, _I, _P]),

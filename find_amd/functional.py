@@ -549,6 +549,66 @@ def contrastive_pose(vecs, codes, pairs, margin=0.5):
 	return _ContrastivePose.apply(vecs, codes, pairs, margin)
 
 
+PART_FORMS = dict(auto=0, direct=1, staged=2)   # FIND_PART_* of find_hip.h
+
+
+def part_labels(gt_logits, size):
+	"""argmax_c of F.interpolate(gt_logits, size, mode='bilinear') -- gt_logits (B, C, h, w) class logits, size (H, W) -> int32 labels
+	(B, H, W), lowest index on ties -- in one pass that never stores the resampled tensor (find_part_labels; reference losses.py:263-265)."""
+	_require_gpu(gt_logits)
+	if gt_logits.dim() != 4:
+		raise RuntimeError(f'find_amd.part_labels: gt_logits (B, C, h, w) expected, got {tuple(gt_logits.shape)}')
+	H, W = (int(s) for s in size)
+	g = _c(gt_logits.detach())
+	B, C, h, w = g.shape
+	labels = torch.empty((B, H, W), device=g.device, dtype=torch.int32)
+	check(_lib.lib().find_part_labels(ptr(g), B, C, h, w, H, W, ptr(labels), current_stream(g.device)), 'find_part_labels')
+	return labels
+
+
+class _PartCrossEntropy(torch.autograd.Function):
+	"""mean over pixels of mask * CE(z, label), z_0 = 100 where mask == 0 else 0, z_c = logits_c for c >= 1 (the reference's cluster loss,
+	losses.py:270-276, 302): find_part_ce_fwd / _bwd.  Gradients go to the logits and the mask; the per-pixel ce * mask is a second,
+	non-differentiable output."""
+
+	@staticmethod
+	def forward(ctx, logits, labels, mask, form):
+		_require_gpu(logits, labels, mask)
+		if logits.dim() < 2 or labels.dtype != torch.int32 or labels.shape != logits.shape[:-1] or mask.shape != logits.shape[:-1]:
+			raise RuntimeError(f'find_amd.part_cross_entropy: logits (..., C), int32 labels (...) and mask (...) expected, got {tuple(logits.shape)} / '
+							   f'{tuple(labels.shape)} {labels.dtype} / {tuple(mask.shape)}')
+		C = logits.shape[-1]
+		P = labels.numel()
+		logits, labels, mask = _c(logits), _c(labels), _c(mask)
+		loss = torch.empty((), device=logits.device, dtype=torch.float32)
+		ce = torch.empty(mask.shape, device=logits.device, dtype=torch.float32)
+		partial = torch.empty((P + 63) // 64, device=logits.device, dtype=torch.float64)   # one block partial per tile of 64 .. 256 pixels
+		check(_lib.lib().find_part_ce_fwd(ptr(logits), ptr(labels), ptr(mask), P, C, ptr(loss), ptr(ce), ptr(partial), form,
+										  current_stream(logits.device)), 'find_part_ce_fwd')
+		ctx.save_for_backward(logits, labels, mask)
+		ctx.form = form
+		ctx.mark_non_differentiable(ce)
+		return loss, ce
+
+	@staticmethod
+	def backward(ctx, g, _g_ce):
+		logits, labels, mask = ctx.saved_tensors
+		d_logits, d_mask = torch.empty_like(logits), torch.empty_like(mask)
+		check(_lib.lib().find_part_ce_bwd(ptr(logits), ptr(labels), ptr(mask), labels.numel(), logits.shape[-1], ptr(_c(g)), ptr(d_logits), ptr(d_mask),
+										  ctx.form, current_stream(logits.device)), 'find_part_ce_bwd')
+		return d_logits, None, d_mask, None
+
+
+def part_cross_entropy(logits, labels, mask, return_ce=False, form='auto'):
+	"""The 2-D part loss on rendered class logits: logits (..., C) channel-last as FootRenderer's out['features'], labels (...) int32
+	(part_labels), mask (...) the soft silhouette.  Channel 0 of the logits is replaced by 100 where mask == 0 and by 0 elsewhere, the
+	softmax cross-entropy is multiplied by the mask and averaged over all pixels (reference losses.py:270-276, 302).  fp32 per pixel
+	with the maximum subtracted, the sum over pixels in double in a fixed order.  return_ce: also the per-pixel ce * mask (no gradient).
+	form: 'auto', or 'direct' / 'staged' to force one kernel form (tools/part_loss_cost.py)."""
+	loss, ce = _PartCrossEntropy.apply(logits, labels, mask, PART_FORMS[form])
+	return (loss, ce) if return_ce else loss
+
+
 class _Register(torch.autograd.Function):
 	"""X = ((verts + disp) * S) @ R(euler XYZ) + t     (model.py:481-491)."""
 

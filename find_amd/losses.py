@@ -2,8 +2,9 @@
 names and forward signatures); the arithmetic runs in libfind_hip.so through find_amd.functional.
 
 In scope: TextureLossGTSpace, DisplacementLoss (Chamfer, incl. the z-cut-off variants),
-MeshSmoothnessLoss, SilhouetteLoss, ContrastiveLoss.  Perceptual / Restyle losses need absent network weights or
-submodules and are out of scope."""
+MeshSmoothnessLoss, SilhouetteLoss, ContrastiveLoss, and the cluster mode of RestylePerceptualLoss on rendered per-vertex class
+logits (the encoder is the caller's).  The other perceptual / Restyle modes need absent network weights or submodules and are out of
+scope."""
 import itertools
 
 import numpy as np
@@ -149,3 +150,53 @@ class ContrastiveLoss(nn.Module):
 		if pairs is None:
 			pairs = pairs_to_device(draw_pairs(N, npairs), vecs.device)
 		return FN.contrastive_pose(vecs, torch.as_tensor(codes).to(device=vecs.device, dtype=torch.float32), pairs)
+
+
+class RestylePerceptualLoss(nn.Module):
+	"""The reference's RestylePerceptualLoss (losses.py:136-302) in the one mode that needs no weights of ours: mode='cluster' on rendered
+	per-vertex class logits (pred_logit).  encoder: the frozen image encoder, any callable used as
+	encoder(images (B, 3, H, W), return_features=True, target_feature_maps=feature_maps)['class_logits'] -> (B, C, h, w); it sees the GT
+	images only, under no_grad.  Everything after its output is two HIP launches forward and one backward (functional.part_labels,
+	functional.part_cross_entropy)."""
+
+	def __init__(self, encoder):
+		super().__init__()
+		if not callable(encoder):
+			raise TypeError('RestylePerceptualLoss(encoder): a callable image encoder is expected')
+		self.encoder = encoder
+
+	def forward(self, pred, gt, mode='feat', feature_maps=None, pred_masks=None, gt_masks=None, debug=False, debug_dir=None, pred_feat=None,
+				pred_logit=None, return_encodings=False):
+		"""pred, gt: renders (B, H, W, 3); pred_logit: rendered class logits (B, H, W, C) CHANNEL-LAST, as the feature render returns them
+		(upstream takes the (B, C, H, W) permutation of the same tensor, model.py:1133); pred_masks (B, H, W): the predicted soft
+		silhouette.  gt_masks is accepted and unused, as upstream.  Returns (loss, encodings); with return_encodings the dictionary holds
+		gt_labels (B, H, W) int32, CE_loss (B, H, W) and gt_logits, the encoder's logits resampled to (H, W) -- formed with F.interpolate
+		on this path only, the loss never needs it."""
+		assert mode in ['feat', 'latent', 'cluster'], f"Mode `{mode}` not understood for Restyle loss."
+		if mode != 'cluster':
+			raise NotImplementedError(f"RestylePerceptualLoss mode='{mode}' compares encoder activations of the predicted render: it needs the "
+									  "encoder's weights and a backward through it, which are out of scope; only mode='cluster' is built")
+		if pred_logit is None:
+			raise NotImplementedError('pred_logit=None would run the encoder on the predicted image and differentiate through it: out of scope; '
+									  'render per-vertex class logits (opts.restyle_cluster_per_vertex) and pass them as pred_logit')
+		if debug:
+			raise NotImplementedError('debug=True writes label images through cv2 (losses.py:283-300): visualisation, out of scope')
+		if feature_maps != [8]:   # (upstream's two refusals, made before the encoder runs instead of after)
+			raise NotImplementedError('Classifier only works with exactly feat map 8 currently.')
+		if pred_masks is None:
+			raise NotImplementedError('Clustering loss requires masking')
+		with torch.no_grad():
+			gt_logit = self.encoder(gt.permute(0, 3, 1, 2), return_features=True, target_feature_maps=feature_maps)['class_logits']
+		H, W = pred.shape[-3], pred.shape[-2]
+		if tuple(pred_logit.shape[:-1]) != (gt_logit.shape[0], H, W) or pred_logit.shape[-1] != gt_logit.shape[1]:
+			raise ValueError(f'RestylePerceptualLoss: pred_logit (B, H, W, C) = {tuple(pred_logit.shape)} does not match the renders '
+							 f'{tuple(pred.shape)} and the encoder\'s class logits {tuple(gt_logit.shape)}')
+		gt_logit = gt_logit.float()
+		gt_labels = FN.part_labels(gt_logit, (H, W))
+		loss, ce = FN.part_cross_entropy(pred_logit, gt_labels, pred_masks, return_ce=True)
+		encodings = {}
+		if return_encodings:
+			encodings['gt_labels'] = gt_labels
+			encodings['gt_logits'] = nn.functional.interpolate(gt_logit, size=(H, W), mode='bilinear')
+			encodings['CE_loss'] = ce
+		return loss, encodings

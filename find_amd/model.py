@@ -252,6 +252,11 @@ class _LazyColours(dict):
 		return dict.__getitem__(self, 'col')
 
 
+def load_template_classes(file, device='cuda'):
+	"""Per-vertex template classes (V, C) of a pretrained checkpoint: its state_dict['features'] (reference model.py:199-203)."""
+	return torch.load(file, map_location=device, weights_only=False)['state_dict']['features'].float()
+
+
 class NeuralDisplacementField(Model):
 	"""Template mesh + Fourier PE + trunk MLP + displacement / colour heads + per-instance latent tables
 	(reference model.py:206-534)."""
@@ -276,8 +281,9 @@ class NeuralDisplacementField(Model):
 						   use_avg_colour=use_avg_colour, latent_labels=latent_labels)
 		if progressive_encoding:
 			raise NotImplementedError('progressive_encoding is flagged untested in the reference (opts.py:49-50) and is out of scope')
-		if restyle_features_per_vertex or restyle_cluster_per_vertex:
-			raise NotImplementedError('restyle per-vertex features are out of scope (need the absent restyle_encoder submodule)')
+		if restyle_features_per_vertex:
+			# (restyle_cluster_per_vertex is only stored, as upstream: ModelWithLoss reads opts.restyle_cluster_per_vertex and res['cpv'])
+			raise NotImplementedError("restyle_features_per_vertex is out of scope: upstream never produces the res['fpv'] it would render (model.py:1081)")
 		if width != 256 or input_dim != 3:
 			raise NotImplementedError('the HIP kernels are specialised for width=256, input_dim=3 (the reference setting, model.py:207)')
 		self.clamp, self.normclamp, self.normratio = clamp, normclamp, normratio
@@ -371,7 +377,10 @@ class NeuralDisplacementField(Model):
 		self.restyle_features_per_vertex = restyle_features_per_vertex
 		self.per_vertex_features = None
 		if opts is not None and getattr(opts, 'template_features_pth', None) is not None:
-			raise NotImplementedError('template_features_pth (per-vertex restyle classes) is out of scope')
+			# per-vertex class logits of the template (model.py:199-203, 377-381): a Parameter in no parameter group, as upstream
+			self.per_vertex_features = nn.Parameter(load_template_classes(opts.template_features_pth, device=device).unsqueeze(0))
+			if template_mesh_loc is not None:
+				self._check_per_vertex_features()
 
 		# --- parameter groups read by train.py:161-168
 		self.main_params = make_params_list(self.base, self.mlp_disp, self.mlp_col, self.shapevec, self.texvec, self.posevec)
@@ -394,6 +403,12 @@ class NeuralDisplacementField(Model):
 		if precision not in (None, 'fp32', 'fp16', 'bf16x3'):
 			raise ValueError(f"set_mlp_precision: None, 'fp32', 'bf16x3' or 'fp16', got {precision!r}")
 		self._spec.precision = precision
+
+	def _check_per_vertex_features(self):
+		f = self.per_vertex_features
+		if f is not None and (f.dim() != 3 or f.shape[1] != self.template_verts.shape[1]):
+			raise ValueError(f'template_features_pth holds per-vertex features of shape {tuple(f.shape[1:])}, the template has '
+							 f'{self.template_verts.shape[1]} vertices: (V, C) with the template\'s V expected')
 
 	def _rebuild_template_mesh(self):
 		self.template_mesh = Meshes(verts=self.template_verts.data, faces=self.template_faces.data[0])
@@ -474,6 +489,7 @@ class NeuralDisplacementField(Model):
 		ModelWithLoss asks for this on steps that render nothing (chamf / smooth / texture read the vertices only; the texture term queries
 		the field at its own samples), where the reference computes the template's colours and drops them.  Same values either way."""
 		N = 0 if shapevec is None else shapevec.shape[0]
+		self._check_per_vertex_features()
 		meshes = extend_template(self.template_mesh, N=N)
 		tv = self.template_verts.data  # (1, V, 3): the trunk is evaluated once for all N feet
 		if not self.use_texvec:
@@ -497,6 +513,8 @@ class NeuralDisplacementField(Model):
 		else:
 			meshes.textures = TexturesVertex(res['col'][..., :3])
 		res.update(meshes=meshes, offsets=offsets, verts=X)
+		if self.per_vertex_features is not None:
+			res['cpv'] = self.per_vertex_features
 		return res
 
 	def get_meshes_from_batch(self, batch, is_train=True, no_displacement=False, lazy_colours=False):
@@ -514,6 +532,7 @@ class NeuralDisplacementField(Model):
 		self.template_verts = nn.Parameter(state_dict['template_verts'].float().to(device), requires_grad=False)
 		self.template_faces = nn.Parameter(state_dict['template_faces'].to(device), requires_grad=False)
 		self._rebuild_template_mesh()
+		self._check_per_vertex_features()
 		if 'avg_col' in state_dict:
 			self.avg_col = nn.Parameter(state_dict['avg_col'].to(device), requires_grad=False)
 

@@ -13,7 +13,7 @@ import torch
 
 from . import functional as FN
 from . import losses as _losses
-from .losses import ContrastiveLoss, DisplacementLoss, MeshSmoothnessLoss, SilhouetteLoss, TextureLossGTSpace
+from .losses import ContrastiveLoss, DisplacementLoss, MeshSmoothnessLoss, RestylePerceptualLoss, SilhouetteLoss, TextureLossGTSpace
 from .model import NeuralDisplacementField, PCAModel
 from .renderer import FootRenderer
 
@@ -25,7 +25,6 @@ OUT_OF_SCOPE_FLAGS = {
 	'vgg_perc': 'perceptual / restyle losses are out of scope (SURVEY.md §2 #4)',
 	'restyle_perc_lat': 'perceptual / restyle losses are out of scope (SURVEY.md §2 #4)',
 	'restyle_perc_feat': 'perceptual / restyle losses are out of scope (SURVEY.md §2 #4)',
-	'restyle_perc_cluster': 'perceptual / restyle losses are out of scope (SURVEY.md §2 #4)',
 	'mask_out_pred_faces': 'mask_out_pred_faces belongs to the VertexFeatures model (out of scope)',
 }
 
@@ -39,6 +38,12 @@ TERMS = (
 	Term('pix', 'loss_pix', 'weight_pix', False, True, '_raw_pix'),
 	Term('sil', 'loss_sil', 'weight_sil', False, True, '_raw_sil'),
 )
+# Terms that read a network of the caller's (ModelWithLoss(restyle_encoder=)): walked after TERMS, which is upstream's insertion order
+# (model.py:1101-1147).  Only the 2-D part loss on rendered per-vertex class logits is built.
+ENCODER_TERMS = (
+	Term('restyle_perc_cluster', 'loss_restyle_perc_cluster', 'weight_restyle_perc_cluster', False, True, '_raw_restyle_perc_cluster'),
+)
+ALL_TERMS = TERMS + ENCODER_TERMS
 
 
 # the GT render on a second stream beside the predicted one (ModelWithLoss._render_gt); FIND_OVERLAP_GT_RENDER=0 turns it off
@@ -141,19 +146,26 @@ def model_from_opts(opts):
 
 class _Step:
 	"""What one forward() call has at hand while the registry is walked."""
-	__slots__ = ('batch', 'epoch', 'opts', 'res', 'is_train', 'use_z_cutoff', 'gt_z_cutoff', 'pred', 'gt', 'gt_chamf', 'gt_tex', 'cont_pairs')
+	__slots__ = ('batch', 'epoch', 'opts', 'res', 'is_train', 'use_z_cutoff', 'gt_z_cutoff', 'pred', 'gt', 'gt_chamf', 'gt_tex', 'cont_pairs', 'restyle_feature_maps', 'encodings')
 
 
 class ModelWithLoss(nn.Module):
-	def __init__(self, *args, opts=None, device='cuda', **kwargs):
+	def __init__(self, *args, opts=None, device='cuda', restyle_encoder=None, **kwargs):
+		"""restyle_encoder (not in the reference, which loads its own from opts.restyle_encoder_path): the frozen image encoder of the 2-D part
+		loss, see losses.RestylePerceptualLoss; it is not passed on to the model class."""
 		super().__init__()
 		cls = model_class_from_opts(opts)
 		if opts.load_model:
 			self.model = cls.load(opts.load_model, device=device, **kwargs, opts=opts)
 		else:
 			self.model = cls(*args, **kwargs, device=device, opts=opts)
-		if opts.vgg_perc_loss or opts.use_restyle():
+		if opts.vgg_perc_loss or opts.restyle_perc_lat_loss or opts.restyle_perc_feat_loss:
 			raise NotImplementedError('VGG / Restyle perceptual losses need network weights that are not available; out of scope')
+		self.restyle_perc_loss = None
+		if opts.restyle_perc_cluster_loss:
+			self._require_part_loss(opts, restyle_encoder)
+		if restyle_encoder is not None:
+			self.restyle_perc_loss = RestylePerceptualLoss(restyle_encoder)
 		self.device = device
 		self.def_loss = DisplacementLoss()
 		self.col_loss = TextureLossGTSpace()
@@ -181,6 +193,27 @@ class ModelWithLoss(nn.Module):
 	def _raw_cont_pose(self, st):
 		# (pairs drawn at the top of forward(), before the camera poses: the reference's numpy order, model.py:1042-1071)
 		return self.contrastive_loss(st.batch['posevec_train' if st.is_train else 'posevec_val'], st.batch['pose_code'], pairs=st.cont_pairs)
+
+	@staticmethod
+	def _require_part_loss(opts, encoder):
+		"""What restyle_perc_cluster needs: the caller's encoder and rendered per-vertex classes (the only pred_logit that is built)."""
+		if encoder is None:
+			raise NotImplementedError('restyle_perc_cluster reads class logits of the GT renders from a frozen image encoder whose weights are not part of '
+									  'this package: pass it as ModelWithLoss(..., restyle_encoder=callable) (losses.RestylePerceptualLoss)')
+		if not getattr(opts, 'restyle_cluster_per_vertex', False):
+			raise NotImplementedError('restyle_perc_cluster without opts.restyle_cluster_per_vertex runs the encoder on the predicted image and '
+									  'differentiates through it: out of scope; set restyle_cluster_per_vertex and template_features_pth')
+		if getattr(opts, 'restyle_no_masking', False):
+			raise NotImplementedError('Clustering loss requires masking')   # (upstream raises this inside the loss, losses.py:267-268)
+
+	def _raw_restyle_perc_cluster(self, st):
+		# (model.py:1129-1147; the rendered logits stay channel-last: upstream's permutation is folded into the kernels)
+		N, M, H, W, _ = st.gt['image'].shape
+		loss, st.encodings = self.restyle_perc_loss(st.pred['image'].view(-1, H, W, 3), st.gt['image'].view(-1, H, W, 3), mode='cluster',
+													 feature_maps=st.restyle_feature_maps, return_encodings=st.encodings is not None,
+													 pred_logit=st.pred['features'].reshape(N * M, H, W, -1),
+													 gt_masks=st.gt['mask'].view(N * M, H, W), pred_masks=st.pred['mask'].view(N * M, H, W))
+		return loss
 
 	def _raw_pix(self, st):
 		# images are compared inside the silhouettes only (model.py:1101-1105): MSE(image * mask, gt image * gt mask), one pass each way
@@ -234,8 +267,11 @@ class ModelWithLoss(nn.Module):
 						  masked_faces=masked_faces, return_mask_out_masks=True)
 		return gt, R, T, side
 
-	def _render_pred(self, st, gt, R, T, side, copy_mask_out, images=True, mask_image=True):
-		pred = self.rdr(st.res['meshes'], R, T, return_images=images, return_mask=True, mask_with_grad=True)
+	def _render_pred(self, st, gt, R, T, side, copy_mask_out, images=True, mask_image=True, features=None):
+		# features: per-vertex class logits (1, V, C) rendered beside the mask (model.py:1077-1081), shared by the N feet -- upstream hands
+		# the renderer the (1, V, C) tensor, which only works at N = 1; the expansion's backward sums over the feet
+		feat = {} if features is None else dict(return_features=True, features=features.expand(len(st.res['meshes']), -1, -1))
+		pred = self.rdr(st.res['meshes'], R, T, return_images=images, return_mask=True, mask_with_grad=True, **feat)
 		if side is not None:
 			main = torch.cuda.current_stream(side.device)
 			for t in gt.values():   # allocated on the second stream, read on this one from here on
@@ -248,6 +284,9 @@ class ModelWithLoss(nn.Module):
 			if images and mask_image:
 				pred['image'] = torch.where(hidden.unsqueeze(-1), torch.ones_like(pred['image']), pred['image'])
 			pred['mask'] = torch.where(hidden, torch.zeros_like(pred['mask']), pred['mask'])
+			# (model.py:1095-1096; the part loss reads the features through the mask, which is zero there: zeroed for a caller who looks)
+			if features is not None and mask_image:
+				pred['features'] = torch.where(hidden.unsqueeze(-1), torch.zeros_like(pred['features']), pred['features'])
 		return pred
 
 	def forward(self, batch, epoch, opts, chamf=False, smooth=False, texture=False, pix=False, vgg_perc=False, sil=False,
@@ -255,8 +294,7 @@ class ModelWithLoss(nn.Module):
 				save_renders=False, render_dir='_pix', is_train=True, use_z_cutoff=False, gt_z_cutoff=None, restyle_feature_maps=None,
 				no_displacement=False, return_renders=False, copy_mask_out=True, mask_out_pred_faces=False, views=None,
 				cont_pairs=None):
-		given = dict(vgg_perc=vgg_perc, restyle_perc_lat=restyle_perc_lat, restyle_perc_feat=restyle_perc_feat, restyle_perc_cluster=restyle_perc_cluster,
-					 mask_out_pred_faces=mask_out_pred_faces)
+		given = dict(vgg_perc=vgg_perc, restyle_perc_lat=restyle_perc_lat, restyle_perc_feat=restyle_perc_feat, mask_out_pred_faces=mask_out_pred_faces)
 		for name, why in OUT_OF_SCOPE_FLAGS.items():
 			if given[name]:
 				raise NotImplementedError(why)
@@ -264,6 +302,8 @@ class ModelWithLoss(nn.Module):
 			# (upstream ends in an AttributeError inside TextureLossGTSpace, losses.py:22-57)
 			raise NotImplementedError('texture=True: the texture loss queries the model\'s colour field, and the PCA model (model_type=\'pca\') has '
 									  'none; switch the texture term off for it')
+		if restyle_perc_cluster:
+			self._require_part_loss(opts, None if self.restyle_perc_loss is None else self.restyle_perc_loss.encoder)
 		# The contrastive pose term (model.py:1042-1049): a batch without pose rows is an error whatever its size; one scan gives no term.
 		# Its pairs are drawn HERE, before anything else draws from numpy's global generator: upstream shuffles them before sampling the
 		# camera poses (model.py:1060-1071).  cont_pairs (not in the reference): device int32 (P, 2) pairs already drawn -- the captured
@@ -275,10 +315,13 @@ class ModelWithLoss(nn.Module):
 				raise ValueError("Contrastive pose loss used, but no pose found")
 			if batch['pose_code'].shape[0] > 1:
 				pairs = cont_pairs if cont_pairs is not None else _losses.pairs_to_device(_losses.draw_pairs(batch['pose_code'].shape[0]), batch[pvec].device)
-		enabled = dict(chamf=chamf, smooth=smooth, texture=texture, cont_pose=pairs is not None, pix=pix, sil=sil)
+		enabled = dict(chamf=chamf, smooth=smooth, texture=texture, cont_pose=pairs is not None, pix=pix, sil=sil,
+					   restyle_perc_cluster=restyle_perc_cluster)
 
 		st = _Step()
 		st.cont_pairs = pairs
+		st.restyle_feature_maps = restyle_feature_maps
+		st.encodings = {} if return_renders else None   # (a dictionary: the part loss is asked for its encodings, model.py:1143-1147)
 		st.batch, st.epoch, st.opts, st.is_train = batch, epoch, opts, is_train
 		st.use_z_cutoff, st.gt_z_cutoff = use_z_cutoff, gt_z_cutoff
 		# train_network asks for renders whenever a checkpoint is saved (train.py:58-66: save_renders at epoch 0, every *_save_every epochs
@@ -286,7 +329,7 @@ class ModelWithLoss(nn.Module):
 		rendering = bool(render_foot or save_renders)
 		# the images (shading, vertex normals) are rendered only when something reads them: the pixel loss, the caller or the PNG (the
 		# reference renders them regardless, renderer.py:290-291; nothing downstream can tell)
-		images = rendering and bool(pix or return_renders or save_renders)
+		images = rendering and bool(pix or restyle_perc_cluster or return_renders or save_renders)   # (the encoder reads the GT image)
 		# The colours of the predicted mesh are read by the image render only: a step that renders no image -- nothing at all, or silhouettes
 		# alone -- leaves the colour head of the template pass to whoever reads res['col'] / meshes.textures first (model.get_meshes:
 		# lazy_colours): nobody, on the 3-D-loss stages and on a silhouette-loss step.
@@ -332,9 +375,14 @@ class ModelWithLoss(nn.Module):
 		st.pred = st.gt = None
 		if rendering:
 			st.gt, R, T, side = self._render_gt(st, views, batch.get('masked_faces', None), images)
-			st.pred = self._render_pred(st, st.gt, R, T, side, copy_mask_out, images, mask_image=bool(return_renders or save_renders))
+			part = rendering and restyle_perc_cluster
+			if part and 'cpv' not in st.res:
+				raise ValueError("restyle_perc_cluster with restyle_cluster_per_vertex renders res['cpv'], and the model has no per-vertex "
+								 'classes: set opts.template_features_pth')
+			st.pred = self._render_pred(st, st.gt, R, T, side, copy_mask_out, images, mask_image=bool(return_renders or save_renders),
+										features=st.res['cpv'] if part else None)
 		raw, weights = {}, []
-		active = [t for t in TERMS if enabled[t.flag] and not (t.needs_3d and not supervise_3d) and not (t.needs_render and not rendering)]
+		active = [t for t in ALL_TERMS if enabled[t.flag] and not (t.needs_3d and not supervise_3d) and not (t.needs_render and not rendering)]
 		# The Chamfer term -- surface sampling and a brute-force nearest-neighbour search: packed fp32 VALU work, no matrix pipe -- beside the
 		# texture term's MLP pass (matrix pipe) on a second stream: they want different halves of a CU.  Autograd replays each term's
 		# backward on the stream of its forward, so the two backward halves overlap as well.  Not under stream capture.
@@ -398,7 +446,7 @@ class ModelWithLoss(nn.Module):
 		else:
 			loss, losses = 0, {}   # sum({}.values()) of the reference: the trainer's `if loss == 0: continue` (trainer.py:108) relies on it
 		if return_renders and rendering:
-			return loss, losses, dict(pred=st.pred, gt=st.gt)
+			return loss, losses, dict(pred=st.pred, gt=st.gt, **(st.encodings or {}))
 		return loss, losses
 
 	@staticmethod

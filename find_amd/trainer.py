@@ -120,6 +120,8 @@ class Trainer:
 			return 'opts.step_per_epoch accumulates gradients over the epoch'
 		if getattr(o, 'restrict_3d_n_train', None) is not None or getattr(o, 'restrict_3d_train_key', None) is not None:
 			return 'per-scan 3-D supervision switches are read on the host'
+		if model_kwargs.get('restyle_perc_cluster'):
+			return 'the restyle_perc_cluster term runs the caller\'s image encoder (ModelWithLoss(restyle_encoder=)): torch code that is not checked for capture'
 		if not any(model_kwargs.get(k) for k in ('chamf', 'smooth', 'texture', 'cont_pose', 'pix', 'sil')):
 			return 'no loss term enabled'
 		for op in optims:

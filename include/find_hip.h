@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define FIND_ABI_VERSION 2
+#define FIND_ABI_VERSION 3
 
 #define FIND_OK 0
 #define FIND_EINVAL (-1)   /* bad argument / unsupported configuration */
@@ -261,6 +261,33 @@ int find_contrastive_fwd(const float* vecs, int64_t N, int64_t K, const float* c
 						 float* loss_out, float* coef_ws, void* stream);
 int find_contrastive_bwd(const float* vecs, int64_t N, int64_t K, const int32_t* pairs, int64_t P, const float* coef_ws, const float* d_loss,
 						 float* d_vecs, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * 2-D part loss.  Replaces everything RestylePerceptualLoss.forward(mode='cluster', pred_logit=...) does after the encoder
+ * (src/model/losses.py:251-302; call site src/model/model.py:1129-1147).
+ * find_part_labels: gt_logits (B, C, h, w) fp32 NCHW -> labels (B, H, W) int32 = argmax_c of the bilinear resample to (H, W) with
+ *   F.interpolate's defaults (align_corners=False: src = (dst + 0.5) * in / out - 0.5, clamped at 0), lowest index on ties (a NaN counts
+ *   as the maximum, as torch.argmax); the resampled tensor is never stored.
+ * find_part_ce_fwd: logits (P, C) fp32 channel-last (a feature render, P = B*H*W pixels), labels (P) int32, mask (P) fp32:
+ *   z_0 = 100 where mask == 0, else 0 (the rendered channel 0 is never read);  z_c = logits_c, c >= 1;
+ *   ce = logsumexp_c z - z_label;  ce_out (P) = ce * mask;  *loss_out = sum_p ce_out / P.
+ *   Per-pixel arithmetic is fp32 with the maximum subtracted; the sum over pixels is double in a fixed order -- one partial per
+ *   workgroup in partial_ws (cdiv(P, 64) doubles), then one workgroup adds the partials -- so two runs agree bit for bit (no atomics).
+ * find_part_ce_bwd: d_logits (P, C) and d_mask (P) are overwritten (plain stores, every element; channel 0 gets zeros):
+ *   d_logits_c = *d_loss / P * mask * (softmax(z)_c - [c == label]),  d_mask = *d_loss / P * ce   (ce recomputed: ce_out holds ce * mask).
+ * A label outside [0, C) gives NaN (ce_out, the loss, that pixel's d_logits and d_mask): nothing is read through it.
+ * form: FIND_PART_AUTO picks FIND_PART_STAGED (a tile of 64 .. 256 pixels through LDS, 16-byte global loads and stores, odd row pitch)
+ *   when a 64-pixel tile fits 40 KiB and the pointers are 16-byte aligned, else FIND_PART_DIRECT (a lane walks its pixel's C floats in
+ *   global memory); the other two values force a form (tools/part_loss_cost.py measures both) and FIND_PART_STAGED refuses what does not fit.
+ * ---------------------------------------------------------------------------------------------- */
+#define FIND_PART_AUTO 0
+#define FIND_PART_DIRECT 1
+#define FIND_PART_STAGED 2
+int find_part_labels(const float* gt_logits, int64_t B, int64_t C, int64_t h, int64_t w, int64_t H, int64_t W, int32_t* labels, void* stream);
+int find_part_ce_fwd(const float* logits, const int32_t* labels, const float* mask, int64_t P, int64_t C, float* loss_out, float* ce_out,
+					 double* partial_ws, int64_t form, void* stream);
+int find_part_ce_bwd(const float* logits, const int32_t* labels, const float* mask, int64_t P, int64_t C, const float* d_loss, float* d_logits,
+					 float* d_mask, int64_t form, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Similarity registration  X = ((v + disp) * S) @ R(euler 'XYZ') + t.
