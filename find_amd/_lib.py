@@ -80,6 +80,13 @@ PROTOTYPES = {
 	'find_part_labels': (c_int, [_P, _I, _I, _I, _I, _I, _I, _P, _P]),
 	'find_part_ce_fwd': (c_int, [_P, _P, _P, _I, _I, _P, _P, _P, _I, _P]),
 	'find_part_ce_bwd': (c_int, [_P, _P, _P, _I, _I, _P, _P, _P, _I, _P]),
+	'find_vertex_normals_fwd': (c_int, [_P, _P, _I, _P, _P, _I, _I, _I, _P, _P]),
+	'find_vertex_normals_bwd': (c_int, [_P, _P, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
+	'find_normal_map_fwd': (c_int, [_P, _P, _I, _I, _I, _I, c_int, _P, _P]),
+	'find_normal_map_bwd': (c_int, [_P, _P, _P, _I, _I, _I, _I, c_int, _P, _P]),
+	'find_normal_loss_ws_bytes': (c_int64, [_I]),
+	'find_normal_loss_fwd': (c_int, [_P, _P, _P, _I, _P, _P, _I, _P]),
+	'find_normal_loss_bwd': (c_int, [_P, _P, _P, _I, _P, _P, _P, _P]),
 	'find_uv_sample': (c_int, [_P, _I, _I, _I, _P, _I, _P, _I, _I, _P, _P, _I, _I, _P, _P]),
 	'find_render_frags': (c_int, [POINTER(RenderParams), _I, _I, _I, _I, _P, _P, _P, _P]),
 	'find_adam_step': (c_int, [_I, _P, _P, _P, _P, _P, c_float, c_float, c_float, c_float, c_float, _I, _P]),

@@ -1228,6 +1228,146 @@ def mesh_smoothness_loss(verts, topo, w_edge=10.0, w_lap=0.1):
 	return _SmoothLoss.apply(verts, topo, float(w_edge), float(w_lap))
 
 
+# ----------------------------------------------------------------------------------------------- surface normals
+def _corner_tables(faces, n_verts):
+	"""Vertex -> incident-corner tables of per-mesh faces (B, F, 3) int32 (rows of -1 pad), built on the device without a host round trip --
+	a captured step can rebuild them on replay: a stable sort of the 3 F corner indices (anything outside [0, V) sorts to the end), the
+	offsets by binary search.  Returns vf_off (B, V + 1), vf_items (B, 3 F) int32; item = face * 3 + corner, ascending per vertex, which is
+	the order MeshTopology lists them in."""
+	B, F, _ = faces.shape
+	key = faces.reshape(B, 3 * F).long()
+	key = torch.where((key < 0) | (key >= n_verts), torch.full_like(key, n_verts), key)
+	skey, order = torch.sort(key, dim=1, stable=True)
+	probe = torch.arange(n_verts + 1, device=faces.device).expand(B, -1).contiguous()
+	return torch.searchsorted(skey, probe, out_int32=True).contiguous(), order.to(torch.int32).contiguous()
+
+
+class _VertexNormals(torch.autograd.Function):
+	@staticmethod
+	def forward(ctx, verts, faces, vf_off, vf_items):
+		L = _lib.lib()
+		verts = _c(verts)
+		N, V, _ = verts.shape
+		fb, F = (1, faces.shape[0]) if faces.dim() == 2 else faces.shape[:2]
+		out = torch.empty_like(verts)
+		check(L.find_vertex_normals_fwd(ptr(verts), ptr(faces), fb, ptr(vf_off), ptr(vf_items), N, V, F, ptr(out), current_stream(verts.device)),
+			  'find_vertex_normals_fwd')
+		ctx.dims = (N, V, F, fb)
+		ctx.save_for_backward(verts, faces, vf_off, vf_items)
+		return out
+
+	@staticmethod
+	def backward(ctx, g):
+		verts, faces, vf_off, vf_items = ctx.saved_tensors
+		N, V, F, fb = ctx.dims
+		d, ws = torch.empty_like(verts), torch.empty_like(verts)
+		check(_lib.lib().find_vertex_normals_bwd(ptr(verts), ptr(faces), fb, ptr(vf_off), ptr(vf_items), N, V, F, ptr(_c(g)), ptr(ws), ptr(d),
+												 current_stream(verts.device)), 'find_vertex_normals_bwd')
+		return d, None, None, None
+
+
+def vertex_normals(verts, faces):
+	"""PyTorch3D's Meshes.verts_normals_padded: verts (N, V, 3); faces (F, 3) shared, or (N, F, 3) per mesh with rows of -1 padding the
+	shorter ones -> (N, V, 3) unit normals, n_v = s_v / max(|s_v|, 1e-6) with s_v the sum of (v1 - v0) x (v2 - v0) over the faces at v; a
+	vertex no face touches gets (0, 0, 0).  A gather over a vertex -> corner table (MeshTopology's for a shared topology, built once per
+	faces tensor; a device sort per call for per-mesh faces), no atomics: two calls agree bit for bit, forward and backward.
+	Differentiable in the vertices."""
+	_require_gpu(verts, faces)
+	if verts.dim() != 3 or verts.shape[-1] != 3 or faces.dim() not in (2, 3) or faces.shape[-1] != 3 or faces.is_floating_point():
+		raise RuntimeError(f'find_amd.vertex_normals: verts (N, V, 3) and integer faces (F, 3) or (N, F, 3) expected, got {tuple(verts.shape)} / '
+						   f'{tuple(faces.shape)} {faces.dtype}')
+	N, V, _ = verts.shape
+	if faces.dim() == 2:
+		topo = MeshTopology.get(faces, V)
+		return _VertexNormals.apply(verts, topo.faces, topo.vf_off, topo.vf_items)
+	if faces.shape[0] not in (1, N):
+		raise RuntimeError(f'find_amd.vertex_normals: {faces.shape[0]} face lists for {N} meshes')
+	f = _faces_i32(faces)
+	off, items = _corner_tables(f, V)
+	return _VertexNormals.apply(verts, f, off, items)
+
+
+class _NormalMap(torch.autograd.Function):
+	@staticmethod
+	def forward(ctx, raw, R, n_views, world):
+		raw, R = _c(raw), _c(R)
+		H, W = raw.shape[-3], raw.shape[-2]
+		n_img = raw.numel() // (H * W * 3)
+		out = torch.empty_like(raw)
+		check(_lib.lib().find_normal_map_fwd(ptr(raw), ptr(R), n_img, n_views, H, W, int(world), ptr(out), current_stream(raw.device)),
+			  'find_normal_map_fwd')
+		ctx.dims = (n_img, n_views, H, W, int(world))
+		ctx.save_for_backward(raw, R)
+		return out
+
+	@staticmethod
+	def backward(ctx, g):
+		raw, R = ctx.saved_tensors
+		n_img, n_views, H, W, world = ctx.dims
+		d = torch.empty_like(raw)
+		check(_lib.lib().find_normal_map_bwd(ptr(raw), ptr(R), ptr(_c(g)), n_img, n_views, H, W, world, ptr(d), current_stream(raw.device)),
+			  'find_normal_map_bwd')
+		return d, None, None, None
+
+
+def normal_map(raw, R, space='view'):
+	"""Unit normal maps from a blended map of world-space normals -- raw (N, M, H, W, 3) or (N * M, H, W, 3), e.g. FootRenderer's feature
+	render of vertex_normals; image = mesh * M + view: n = raw / |raw|, then n @ R[view] with R (M, 3, 3) the cameras' rotations
+	(p_view = p_world @ R).  space='world' skips the rotation (R may be None).  Output and gradient are 0 where |raw| <= 1e-6 (background).
+	Differentiable in raw."""
+	if space not in ('view', 'world'):
+		raise ValueError(f"find_amd.normal_map: space 'view' or 'world', got {space!r}")
+	world = space == 'world'
+	_require_gpu(raw, None if world else R)
+	if raw.dim() not in (4, 5) or raw.shape[-1] != 3:
+		raise RuntimeError(f'find_amd.normal_map: raw (N, M, H, W, 3) or (N * M, H, W, 3) expected, got {tuple(raw.shape)}')
+	if world:
+		return _NormalMap.apply(raw, None, 1, True)
+	if R is None or R.dim() != 3 or tuple(R.shape[1:]) != (3, 3):
+		raise RuntimeError("find_amd.normal_map: R (M, 3, 3) expected (space='world' needs none)")
+	M = R.shape[0]
+	if (raw.dim() == 5 and raw.shape[1] != M) or (raw.dim() == 4 and raw.shape[0] % M):
+		raise RuntimeError(f'find_amd.normal_map: raw {tuple(raw.shape)} does not hold images of {M} views')
+	return _NormalMap.apply(raw, R.detach(), M, False)
+
+
+class _NormalLoss(torch.autograd.Function):
+	@staticmethod
+	def forward(ctx, pred, target, weight):
+		L = _lib.lib()
+		pred, target, weight = _c(pred), _c(target), _c(weight)
+		P = weight.numel()
+		nbytes = L.find_normal_loss_ws_bytes(P)
+		if nbytes < 0:
+			check(-1, 'find_normal_loss_ws_bytes')
+		ws = torch.empty((nbytes + 7) // 8, device=pred.device, dtype=torch.float64)   # sum w (read by the backward) and the block partials
+		loss = torch.empty((), device=pred.device, dtype=torch.float32)
+		check(L.find_normal_loss_fwd(ptr(pred), ptr(target), ptr(weight), P, ptr(loss), ptr(ws), ws.numel() * 8, current_stream(pred.device)),
+			  'find_normal_loss_fwd')
+		ctx.save_for_backward(pred, target, weight, ws)
+		return loss
+
+	@staticmethod
+	def backward(ctx, g):
+		pred, target, weight, ws = ctx.saved_tensors
+		d = torch.empty_like(pred)
+		check(_lib.lib().find_normal_loss_bwd(ptr(pred), ptr(target), ptr(weight), weight.numel(), ptr(_c(g)), ptr(ws), ptr(d),
+											  current_stream(pred.device)), 'find_normal_loss_bwd')
+		return d, None, None
+
+
+def normal_loss(pred, target, weight):
+	"""Weighted cosine loss between two normal maps: pred, target (..., 3), not necessarily unit (raw blended maps will do: a rotation
+	common to both cancels), weight (...) >= 0 without gradient:  sum_i w_i (1 - p^_i . t^_i) / max(sum_i w_i, 1e-12), the cosine taken as 0
+	(and no gradient) where |p_i| <= 1e-6 or |t_i| <= 1e-6.  One pass each way and a fixed-order sum in double (find_normal_loss_*): two
+	runs agree bit for bit; all-zero weights give 0 and a zero gradient.  The gradient goes to pred only."""
+	_require_gpu(pred, target, weight)
+	if pred.dim() < 1 or pred.shape[-1] != 3 or target.shape != pred.shape or tuple(weight.shape) != tuple(pred.shape[:-1]) or pred.numel() == 0:
+		raise RuntimeError(f'find_amd.normal_loss: pred and target (..., 3) and weight (...) expected, got {tuple(pred.shape)} / {tuple(target.shape)} / '
+						   f'{tuple(weight.shape)}')
+	return _NormalLoss.apply(pred, target.detach(), weight.detach())
+
+
 # Default arithmetic of the 256 -> 256 layers: 'bf16x3' (fp32-faithful on the bf16 matrix pipe; set_mlp_precision below says what that is);
 # FIND_MLP_PRECISION=fp32 selects the fp32 MFMA kernels (A/B runs, the bench's comparison record)
 _MLP_PRECISION = _os.environ.get('FIND_MLP_PRECISION', 'bf16x3')

@@ -200,3 +200,13 @@ class RestylePerceptualLoss(nn.Module):
 			encodings['gt_logits'] = nn.functional.interpolate(gt_logit, size=(H, W), mode='bilinear')
 			encodings['CE_loss'] = ce
 		return loss, encodings
+
+
+class NormalLoss(nn.Module):
+	"""Weighted cosine loss between a predicted and a target normal map (not in the reference; FOUND-style fitting to surface normals): one
+	HIP pass each way (functional.normal_loss)."""
+
+	def forward(self, pred, target, weight):
+		"""pred, target (..., 3), not necessarily unit; weight (...) without gradient: sum w (1 - cos) / max(sum w, 1e-12).  The gradient
+		goes to pred only."""
+		return FN.normal_loss(pred, target, weight)

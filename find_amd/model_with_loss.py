@@ -13,7 +13,7 @@ import torch
 
 from . import functional as FN
 from . import losses as _losses
-from .losses import ContrastiveLoss, DisplacementLoss, MeshSmoothnessLoss, RestylePerceptualLoss, SilhouetteLoss, TextureLossGTSpace
+from .losses import ContrastiveLoss, DisplacementLoss, MeshSmoothnessLoss, NormalLoss, RestylePerceptualLoss, SilhouetteLoss, TextureLossGTSpace
 from .model import NeuralDisplacementField, PCAModel
 from .renderer import FootRenderer
 
@@ -44,6 +44,11 @@ ENCODER_TERMS = (
 	Term('restyle_perc_cluster', 'loss_restyle_perc_cluster', 'weight_restyle_perc_cluster', False, True, '_raw_restyle_perc_cluster'),
 )
 ALL_TERMS = TERMS + ENCODER_TERMS
+# Terms the reference does not have, walked after ALL_TERMS.  normal: the cosine loss between the rendered surface normals of the prediction
+# and of the GT scans (forward(normal=True); callers pass the flag in model_kwargs, Opts.net_train_kwargs keeps upstream's ten keys).
+EXTENSION_TERMS = (
+	Term('normal', 'loss_normal', 'weight_normal', False, True, '_raw_normal'),
+)
 
 
 # the GT render on a second stream beside the predicted one (ModelWithLoss._render_gt); FIND_OVERLAP_GT_RENDER=0 turns it off
@@ -174,6 +179,7 @@ class ModelWithLoss(nn.Module):
 		self.pix_loss = nn.MSELoss()      # (attributes of the reference; the forward computes both losses through find_image_mse_*)
 		self.sil_loss = SilhouetteLoss()
 		self.contrastive_loss = ContrastiveLoss()
+		self.normal_loss = NormalLoss()
 		# (max_faces_per_bin only sizes PyTorch3D's coarse bins -- 30 000 for the full-resolution scans, model.py:987; no effect on results)
 		self.rdr = FootRenderer(image_size=256, device=device, bin_size=None, max_faces_per_bin=None if opts.low_poly_meshes else 30000)
 
@@ -215,6 +221,11 @@ class ModelWithLoss(nn.Module):
 													 gt_masks=st.gt['mask'].view(N * M, H, W), pred_masks=st.pred['mask'].view(N * M, H, W))
 		return loss
 
+	def _raw_normal(self, st):
+		# both maps are the raw world-space blends of the step's shared cameras: the rotation into a view cancels in the dot product and the
+		# loss normalises, so neither goes through normal_map.  A pixel counts by how much both silhouettes cover it; the weight has no gradient.
+		return self.normal_loss(st.pred['normals_raw'], st.gt['normals_raw'], st.gt['mask'] * st.pred['mask'].detach())
+
 	def _raw_pix(self, st):
 		# images are compared inside the silhouettes only (model.py:1101-1105): MSE(image * mask, gt image * gt mask), one pass each way
 		# (find_image_mse_*; CPU tensors raise there: no fallback)
@@ -246,7 +257,7 @@ class ModelWithLoss(nn.Module):
 			return False
 		return True
 
-	def _render_gt(self, st, views, masked_faces, images=True):
+	def _render_gt(self, st, views, masked_faces, images=True, normals=False):
 		"""The GT render of a step: (gt, R, T, second stream or None).  It carries no gradient and reads nothing of the prediction, so it
 		runs on a second stream beside the predicted render: C3 step 8.3 -> 7.8 ms (the two rasteriser launches share the chip
 		5 % better than they use it alone, and the predicted render's small launches run under the GT render's tail).  (Issued before the
@@ -263,15 +274,28 @@ class ModelWithLoss(nn.Module):
 			side.wait_stream(torch.cuda.current_stream(dev))
 		with torch.no_grad(), (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
 			# the GT scans are rendered again every step, as the reference does (model.py:1073-1075)
+			# (normals: the scans' vertex normals as three feature channels of the same raster pass -- gt['normals_raw'], the raw blend)
+			feat = dict(return_features=True, features=st.batch['mesh'].verts_normals_padded()) if normals else {}
 			gt = self.rdr(st.batch['mesh'], R, T, return_images=images, return_mask=True, mask_with_grad=True, mask_out_faces=True,
-						  masked_faces=masked_faces, return_mask_out_masks=True)
+						  masked_faces=masked_faces, return_mask_out_masks=True, **feat)
+			if normals:
+				gt['normals_raw'] = gt.pop('features')
 		return gt, R, T, side
 
-	def _render_pred(self, st, gt, R, T, side, copy_mask_out, images=True, mask_image=True, features=None):
+	def _render_pred(self, st, gt, R, T, side, copy_mask_out, images=True, mask_image=True, features=None, normals=False):
 		# features: per-vertex class logits (1, V, C) rendered beside the mask (model.py:1077-1081), shared by the N feet -- upstream hands
 		# the renderer the (1, V, C) tensor, which only works at N = 1; the expansion's backward sums over the feet
-		feat = {} if features is None else dict(return_features=True, features=features.expand(len(st.res['meshes']), -1, -1))
+		# normals: the predicted meshes' vertex normals as the first three feature channels of the same raster pass (pred['normals_raw'])
+		chans = [st.res['meshes'].verts_normals_padded()] if normals else []
+		if features is not None:
+			chans.append(features.expand(len(st.res['meshes']), -1, -1))
+		feat = {} if not chans else dict(return_features=True, features=chans[0] if len(chans) == 1 else torch.cat(chans, dim=-1))
 		pred = self.rdr(st.res['meshes'], R, T, return_images=images, return_mask=True, mask_with_grad=True, **feat)
+		if normals:
+			both = pred.pop('features')
+			pred['normals_raw'] = both[..., :3] if features is not None else both
+			if features is not None:
+				pred['features'] = both[..., 3:]
 		if side is not None:
 			main = torch.cuda.current_stream(side.device)
 			for t in gt.values():   # allocated on the second stream, read on this one from here on
@@ -287,13 +311,15 @@ class ModelWithLoss(nn.Module):
 			# (model.py:1095-1096; the part loss reads the features through the mask, which is zero there: zeroed for a caller who looks)
 			if features is not None and mask_image:
 				pred['features'] = torch.where(hidden.unsqueeze(-1), torch.zeros_like(pred['features']), pred['features'])
+			if normals and mask_image:   # (the normal loss weighs by the mask as well)
+				pred['normals_raw'] = torch.where(hidden.unsqueeze(-1), torch.zeros_like(pred['normals_raw']), pred['normals_raw'])
 		return pred
 
 	def forward(self, batch, epoch, opts, chamf=False, smooth=False, texture=False, pix=False, vgg_perc=False, sil=False,
 				restyle_perc_lat=False, restyle_perc_feat=False, restyle_perc_cluster=False, cont_pose=False, render_foot=False,
 				save_renders=False, render_dir='_pix', is_train=True, use_z_cutoff=False, gt_z_cutoff=None, restyle_feature_maps=None,
 				no_displacement=False, return_renders=False, copy_mask_out=True, mask_out_pred_faces=False, views=None,
-				cont_pairs=None):
+				cont_pairs=None, normal=False):
 		given = dict(vgg_perc=vgg_perc, restyle_perc_lat=restyle_perc_lat, restyle_perc_feat=restyle_perc_feat, mask_out_pred_faces=mask_out_pred_faces)
 		for name, why in OUT_OF_SCOPE_FLAGS.items():
 			if given[name]:
@@ -316,7 +342,7 @@ class ModelWithLoss(nn.Module):
 			if batch['pose_code'].shape[0] > 1:
 				pairs = cont_pairs if cont_pairs is not None else _losses.pairs_to_device(_losses.draw_pairs(batch['pose_code'].shape[0]), batch[pvec].device)
 		enabled = dict(chamf=chamf, smooth=smooth, texture=texture, cont_pose=pairs is not None, pix=pix, sil=sil,
-					   restyle_perc_cluster=restyle_perc_cluster)
+					   restyle_perc_cluster=restyle_perc_cluster, normal=normal)
 
 		st = _Step()
 		st.cont_pairs = pairs
@@ -374,15 +400,15 @@ class ModelWithLoss(nn.Module):
 					t.record_stream(main)
 		st.pred = st.gt = None
 		if rendering:
-			st.gt, R, T, side = self._render_gt(st, views, batch.get('masked_faces', None), images)
+			st.gt, R, T, side = self._render_gt(st, views, batch.get('masked_faces', None), images, **(dict(normals=True) if normal else {}))
 			part = rendering and restyle_perc_cluster
 			if part and 'cpv' not in st.res:
 				raise ValueError("restyle_perc_cluster with restyle_cluster_per_vertex renders res['cpv'], and the model has no per-vertex "
 								 'classes: set opts.template_features_pth')
 			st.pred = self._render_pred(st, st.gt, R, T, side, copy_mask_out, images, mask_image=bool(return_renders or save_renders),
-										features=st.res['cpv'] if part else None)
+										features=st.res['cpv'] if part else None, **(dict(normals=True) if normal else {}))
 		raw, weights = {}, []
-		active = [t for t in ALL_TERMS if enabled[t.flag] and not (t.needs_3d and not supervise_3d) and not (t.needs_render and not rendering)]
+		active = [t for t in ALL_TERMS + EXTENSION_TERMS if enabled[t.flag] and not (t.needs_3d and not supervise_3d) and not (t.needs_render and not rendering)]
 		# The Chamfer term -- surface sampling and a brute-force nearest-neighbour search: packed fp32 VALU work, no matrix pipe -- beside the
 		# texture term's MLP pass (matrix pipe) on a second stream: they want different halves of a CU.  Autograd replays each term's
 		# backward on the stream of its forward, so the two backward halves overlap as well.  Not under stream capture.
@@ -433,7 +459,8 @@ class ModelWithLoss(nn.Module):
 				tex_fn._set_sequence_nr(verts_fn._sequence_nr() + 1)
 		for term in active:   # (reported, and summed, in the registry's order whatever the issue order was)
 			raw[term.key] = got[term.key]
-			weights.append(float(getattr(opts, term.weight)))
+			# (a reference Opts knows nothing of an extension term's weight: 1)
+			weights.append(float(getattr(opts, term.weight, 1.) if term in EXTENSION_TERMS else getattr(opts, term.weight)))
 		for side in (aside, third, tex_side):
 			if side is not None:
 				torch.cuda.current_stream(dev).wait_stream(side)

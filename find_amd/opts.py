@@ -29,6 +29,8 @@ class Opts:
 		val_crit='chamf', no_latent_refinement=False, latent_epochs=500, latent_optim='Adam', latent_save_every=250, latent_val_every=25,
 		no_rendering=False, restyle_feature_maps=None, only_classifier_head=False, step_per_epoch=False, net_repeat_dataset=1,
 		render_dir='_pix',
+		# not in the reference: the surface-normal term (ModelWithLoss.forward(normal=True); passed in model_kwargs, not by net_train_kwargs)
+		normal_loss=False, weight_normal=1.,
 	)
 
 	def __init__(self, **kw):

@@ -8,6 +8,7 @@ from typing import Union
 import numpy as np
 import torch
 
+from . import functional as FN
 from . import functional_render as FR
 from .cameras import look_at_view_transform
 from .structures import Meshes, TexturesUV, TexturesVertex
@@ -81,7 +82,7 @@ class FootRenderer(nn.Module):
 	# ------------------------------------------------------------------ render
 	def forward(self, input_meshes: Meshes, R, T, return_images=True, return_depth=False, return_mask=False, mask_with_grad=True,
 				mask_out_faces=False, masked_faces=None, keypoints=None, keypoints_blend=False, lights=None, return_mask_out_masks=False,
-				return_features=False, features=None) -> dict:
+				return_features=False, features=None, return_normals=False, normals_space='view') -> dict:
 		"""Render N meshes from M views: image [N,M,H,W,3], mask [N,M,H,W] (soft silhouette when mask_with_grad), optional
 		depth and mask-out masks (reference renderer.py:247-383).  Image index = mesh*M + view.
 		keypoints (N,P,3): out['keypoints'] (N,M,H,W,3), the points drawn red by PyTorch3D's point renderer (functional_render.render_points;
@@ -93,18 +94,25 @@ class FootRenderer(nn.Module):
 		(renderer.py:293-299: softmax_blend over the K = 100 silhouette fragments, znear 1, zfar 100, background 0), differentiable in the
 		features and the vertices; 0 where mask_out_faces hides a pixel.  Upstream needs return_mask=True as well (fragments['sil'] only
 		exists then); here the silhouette pass runs either way and out['mask'] is returned only when asked for.  Not in split mode
-		(clip_faces=True)."""
+		(clip_faces=True).
+		return_normals (not in the reference): out['normals'] (N,M,H,W,3), unit surface normals in the camera frame of each view
+		(normals_space='view': n_world @ R[view]) or in world space ('world'), 0 on the background and where mask_out_faces hides a pixel:
+		functional.normal_map of the feature render of the mesh's vertex normals (Meshes.verts_normals_padded), so differentiable to the
+		vertices through the normals and through the blend.  Together with return_features the normals are a feature render of their own
+		on a second raster pass: each output is what the call that asks for it alone returns.  Not in split mode either."""
 		if keypoints is not None:
 			if keypoints_blend and not return_images:   # (a NameError upstream)
 				raise ValueError('FootRenderer: keypoints_blend draws the keypoints over the image: it needs return_images=True')
 			if keypoints.dim() != 3 or keypoints.shape[-1] != 3 or keypoints.shape[0] != len(input_meshes):
 				raise ValueError(f'FootRenderer: keypoints must be (N,P,3) with N = {len(input_meshes)} meshes, got {tuple(keypoints.shape)}')
+		if (return_features or return_normals) and self.params.clip_faces:
+			raise NotImplementedError('FootRenderer: per-vertex features are not rendered with clip_faces=True: the feature shader reads '
+									  'the K nearest silhouette candidates of unclipped faces (split mode is out of scope for it)')
+		if return_normals and normals_space not in ('view', 'world'):
+			raise ValueError(f"FootRenderer: normals_space 'view' or 'world', got {normals_space!r}")
 		if return_features:
 			if features is None:   # (an assert upstream)
 				raise ValueError('FootRenderer: return_features needs features (N,V,C)')
-			if self.params.clip_faces:
-				raise NotImplementedError('FootRenderer: per-vertex features are not rendered with clip_faces=True: the feature shader reads '
-										  'the K nearest silhouette candidates of unclipped faces (split mode is out of scope for it)')
 			nv = input_meshes.verts_padded().shape[:2]
 			if (not isinstance(features, torch.Tensor) or not features.is_floating_point() or features.dim() != 3
 					or tuple(features.shape[:2]) != tuple(nv) or features.shape[2] < 1):
@@ -132,19 +140,28 @@ class FootRenderer(nn.Module):
 		want_soft = return_mask and (mask_with_grad or not return_images)
 		# (pix_to_face is read below only to hide faces: when the caller names some, or for UV textures' (0,0)-UV convention)
 		want_frags = (mask_out_faces and (masked_faces is not None or uv_tex)) or return_depth
-		if not (return_images or want_soft or want_frags or return_features):
+		# the normals travel as three feature channels: the call's own feature render when it has no other, else one more (see above)
+		vnormals = input_meshes.verts_normals_padded() if return_normals else None
+		if return_normals and not return_features:
+			features = vnormals
+		with_feat = return_features or return_normals
+		if not (return_images or want_soft or want_frags or with_feat):
 			return self._keypoints(dict(), None, keypoints, keypoints_blend, R, T, dev)
 		if return_images and uv_tex:
 			# GT scans (dataset.py:263-271): no gradient flows to a UV-textured mesh anywhere in the reference
 			if verts.requires_grad:
 				raise NotImplementedError('UV-textured meshes are rendered without gradient (GT scans); use TexturesVertex for predicted meshes')
 			res = FR.render_uv(verts, tex, faces, R, T, self.params, want_mask=want_soft, want_frags=want_frags,
-							   features=features if return_features else None)
+							   features=features if with_feat else None)
 		else:
 			res = FR.render(verts, colors, faces, R, T, self.params, want_mask=want_soft, want_image=return_images, want_frags=want_frags,
-							features=features if return_features else None)
+							features=features if with_feat else None)
 		mask, renders, p2f, zbuf = res[:4]
-		feat = res[4] if return_features else None
+		feat = res[4] if with_feat else None
+		nraw = None
+		if return_normals:
+			nraw = feat if not return_features else FR.render(verts, None, faces, R, T, self.params, want_mask=False, want_image=False,
+															  features=vnormals)[4]
 		out = dict()
 		if return_depth:
 			out['depth'] = zbuf
@@ -175,8 +192,10 @@ class FootRenderer(nn.Module):
 				renders = torch.where(mask_out.unsqueeze(-1), torch.ones_like(renders), renders)
 			if return_mask:
 				mask = torch.where(mask_out, torch.zeros_like(mask), mask)
-			if return_features:   # (renderer.py:361-363)
+			if with_feat:   # (renderer.py:361-363)
 				feat = torch.where(mask_out.unsqueeze(-1), torch.zeros_like(feat), feat)
+			if return_normals:
+				nraw = feat if not return_features else torch.where(mask_out.unsqueeze(-1), torch.zeros_like(nraw), nraw)
 
 		self._keypoints(out, renders, keypoints, keypoints_blend, R, T, dev)
 		if return_images:
@@ -188,6 +207,8 @@ class FootRenderer(nn.Module):
 			out['nothing_hidden'] = nothing_hidden
 		if return_features:
 			out['features'] = feat
+		if return_normals:
+			out['normals'] = FN.normal_map(nraw, R, space=normals_space)
 		return out
 
 	def _keypoints(self, out, renders, keypoints, keypoints_blend, R, T, dev):

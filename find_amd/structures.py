@@ -163,6 +163,12 @@ class Meshes:
 			return self._faces_shared.long().unsqueeze(0).expand(len(self), -1, -1)
 		return self._faces
 
+	def verts_normals_padded(self):
+		"""(N, V, 3) unit vertex normals, PyTorch3D's name and rule (functional.vertex_normals: a HIP gather, differentiable in the
+		vertices); padding vertices, which no face touches, get zeros."""
+		from . import functional as FN
+		return FN.vertex_normals(self._verts, self._faces_shared if self._faces_shared is not None else self._faces)
+
 	def num_verts_per_mesh(self):
 		return torch.tensor(self._num_verts, dtype=torch.int64, device=self.device)
 

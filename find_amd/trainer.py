@@ -122,6 +122,9 @@ class Trainer:
 			return 'per-scan 3-D supervision switches are read on the host'
 		if model_kwargs.get('restyle_perc_cluster'):
 			return 'the restyle_perc_cluster term runs the caller\'s image encoder (ModelWithLoss(restyle_encoder=)): torch code that is not checked for capture'
+		if model_kwargs.get('normal'):
+			return ('the normal term renders the GT scans\' vertex normals, whose vertex -> corner tables are rebuilt every step by a device sort '
+					'(torch.sort, torch.searchsorted): torch code that is not checked for capture')
 		if not any(model_kwargs.get(k) for k in ('chamf', 'smooth', 'texture', 'cont_pose', 'pix', 'sil')):
 			return 'no loss term enabled'
 		for op in optims:

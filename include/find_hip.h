@@ -290,6 +290,38 @@ int find_part_ce_bwd(const float* logits, const int32_t* labels, const float* ma
 					 float* d_mask, int64_t form, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Surface normals (normals.hip): vertex normals, the normal-map stage behind the feature render, a cosine loss between two maps.
+ * No float atomics anywhere: two calls agree bit for bit.
+ * find_vertex_normals_fwd: PyTorch3D's verts_normals_padded.  verts (N, V, 3); faces (faces_batch, F, 3) int32, faces_batch 1 (shared) or
+ *   N (per mesh, rows of -1 pad the shorter ones); vf_off (faces_batch, V + 1) and vf_items (faces_batch, 3 F) int32: the corners
+ *   (item = face * 3 + corner) at every vertex, ascending per vertex -- a CSR table, the caller's (functional.MeshTopology holds one for a
+ *   shared topology).  normals_out (N, V, 3) = s / max(|s|, 1e-6), s = the sum of (v1 - v0) x (v2 - v0) over the vertex's corners in the
+ *   table's order; (0, 0, 0) for a vertex of no face.  A face with an index outside [0, V) contributes nothing.
+ * find_vertex_normals_bwd: d_verts (N, V, 3) overwritten (every element) from d_normals (N, V, 3): through the normalisation
+ *   ((g - n (n . g)) / |s|; g / 1e-6 where |s| <= 1e-6), then through the cross products by the same gather.  d_raw_ws: N * V * 3 floats.
+ * find_normal_map_fwd: raw (n_images, H, W, 3), a blended map of world-space normals -> out = (raw / |raw|) @ R[image % n_views]
+ *   (R (n_views, 3, 3) row-major, p_view = p_world @ R; image = mesh * n_views + view); world != 0 skips the rotation (R may be NULL);
+ *   0 where |raw| <= 1e-6.   find_normal_map_bwd: d_raw (overwritten) from d_out; 0 where |raw| <= 1e-6.
+ * find_normal_loss_fwd: pred, target (P, 3), not necessarily unit; weight (P):  c_i = p^_i . t^_i (0 where |p_i| <= 1e-6 or |t_i| <= 1e-6),
+ *   *loss_out = sum_i w_i (1 - c_i) / max(sum_i w_i, 1e-12).  fp32 per pixel; both sums in double, one pair of partials per workgroup of
+ *   1024 pixels, added by one workgroup in a fixed order.  16-byte loads and stores when pred, target, weight (and d_pred) are 16-byte aligned.
+ *   ws: find_normal_loss_ws_bytes(P) bytes, 8-byte aligned; the backward reads sum_i w_i from it, so it lives until then.
+ * find_normal_loss_bwd: d_pred_i = -*d_loss * w_i / max(sum w, 1e-12) * (t^_i - c_i p^_i) / |p_i|  (overwritten, every element; 0 where c_i
+ *   was forced to 0).  target and weight receive no gradient.
+ * ---------------------------------------------------------------------------------------------- */
+int find_vertex_normals_fwd(const float* verts, const int32_t* faces, int64_t faces_batch, const int32_t* vf_off, const int32_t* vf_items, int64_t N,
+							int64_t V, int64_t F, float* normals_out, void* stream);
+int find_vertex_normals_bwd(const float* verts, const int32_t* faces, int64_t faces_batch, const int32_t* vf_off, const int32_t* vf_items, int64_t N,
+							int64_t V, int64_t F, const float* d_normals, float* d_raw_ws, float* d_verts, void* stream);
+int find_normal_map_fwd(const float* raw, const float* R, int64_t n_images, int64_t n_views, int64_t H, int64_t W, int world, float* out, void* stream);
+int find_normal_map_bwd(const float* raw, const float* R, const float* d_out, int64_t n_images, int64_t n_views, int64_t H, int64_t W, int world,
+						float* d_raw, void* stream);
+int64_t find_normal_loss_ws_bytes(int64_t P);
+int find_normal_loss_fwd(const float* pred, const float* target, const float* weight, int64_t P, float* loss_out, void* ws, int64_t ws_bytes, void* stream);
+int find_normal_loss_bwd(const float* pred, const float* target, const float* weight, int64_t P, const float* d_loss, const void* ws, float* d_pred,
+						 void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Similarity registration  X = ((v + disp) * S) @ R(euler 'XYZ') + t.
  * Replaces euler_angles_to_matrix + Transform3d().scale().rotate().translate().transform_points
  * in NeuralDisplacementField.get_meshes (src/model/model.py:481-491).
