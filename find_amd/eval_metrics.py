@@ -11,7 +11,7 @@ sum of 0 -> nan)."""
 import torch
 
 from . import functional as FN
-from .losses import sample_points_from_meshes
+from .losses import point_mesh_distance, sample_points_from_meshes
 
 # template vertex ids of the six keypoints on the PCA foot model's mesh (reference src/cfg.yaml:11, read by eval_3d.py:137-138 and
 # eval_2d.py:155-156): eval_3d_metrics(..., template_kp_idxs=PCA_KEYPOINTS) for a PCAModel fitted to Foot3D scans
@@ -26,10 +26,15 @@ def keypoint_error_mm(pred_verts, template_kp_idxs, gt_kps):
 
 
 def eval_3d_metrics(pred_meshes, gt_meshes, pred_verts=None, template_kp_idxs=None, gt_kps=None, samples=10000, z_cutoff=0.07,
-					draws_gt=None, draws_pred=None, return_samples=False):
+					draws_gt=None, draws_pred=None, return_samples=False, surface=False, return_per_foot=False):
 	"""Returns {'Keypoint (mm)', 'Chamf z-cutoff <z> (um)', 'Chamf (um)'} as 0-d tensors (keypoints only when given); with return_samples
 	also (gt_pts, pred_pts), the (N,samples,3) surface samples the Chamfer terms were taken on (the per-vertex heat maps of eval_3d.py:171-178
-	read the predicted ones: no second draw)."""
+	read the predicted ones: no second draw).
+	surface (not in the reference): three more keys, distances to the other SURFACE (losses.point_mesh_distance) instead of to its samples --
+	'Scan→pred (mm)': the mean over feet of the mean unsquared distance of every scan vertex to the predicted surface, x 1e3; 'Pred→scan (mm)':
+	the same for the predicted vertices against the scan's surface; 'Surf (μm)': the symmetric mean squared distance of the very samples
+	'Chamf (μm)' used, x 1e6.  return_per_foot (with surface): a last value {'Scan→pred (mm)', 'Pred→scan (mm)'} of (N) tensors, a number per
+	foot."""
 	with torch.no_grad():
 		gt_pts = sample_points_from_meshes(gt_meshes, num_samples=samples, draws=draws_gt)
 		pred_pts = sample_points_from_meshes(pred_meshes, num_samples=samples, draws=draws_pred)
@@ -46,7 +51,20 @@ def eval_3d_metrics(pred_meshes, gt_meshes, pred_verts=None, template_kp_idxs=No
 		out = {f'Chamf z-cutoff {z_cutoff} (μm)': chamf_cut * 1e6, 'Chamf (μm)': chamf * 1e6}
 		if template_kp_idxs is not None:
 			out['Keypoint (mm)'] = keypoint_error_mm(pred_verts, template_kp_idxs, gt_kps)
-	return (out, (gt_pts, pred_pts)) if return_samples else out
+		per_foot = {}
+		if surface:
+			n_gt = gt_meshes.num_verts_per_mesh().to(torch.int32)
+			n_pred = pred_meshes.num_verts_per_mesh().to(torch.int32)
+			to_pred, _, _ = point_mesh_distance(gt_meshes.verts_padded(), pred_meshes, n_gt)      # (padded rows: 0)
+			to_gt, _, _ = point_mesh_distance(pred_meshes.verts_padded(), gt_meshes, n_pred)
+			per_foot['Scan→pred (mm)'] = to_pred.sqrt().sum(1) / n_gt.clamp(min=1) * 1e3
+			per_foot['Pred→scan (mm)'] = to_gt.sqrt().sum(1) / n_pred.clamp(min=1) * 1e3
+			out.update({k: v.mean() for k, v in per_foot.items()})
+			s_pred, _, _ = point_mesh_distance(gt_pts, pred_meshes)
+			s_gt, _, _ = point_mesh_distance(pred_pts, gt_meshes)
+			out['Surf (μm)'] = (s_pred.mean(1) + s_gt.mean(1)).mean() * 1e6
+	ret = (out,) + (((gt_pts, pred_pts),) if return_samples else ()) + ((per_foot,) if surface and return_per_foot else ())
+	return ret if len(ret) > 1 else out
 
 
 # ---------------------------------------------------------------------------------------------- 2-D (eval_2d.py, eval_metrics.py)

@@ -69,7 +69,7 @@ def eval_2d(model, dataset, image_size=128, nviews=1, batch_size=1, R=None, T=No
 
 def eval_3d(model, dataset, template_kp_idxs, samples=10000, z_cutoff=0.07, feet_per_call=16, render_correspondences=False, image_size=256,
 			return_per_foot=False, device='cuda', produce_spins=False, export_meshes=False, out_dir=None, spin_frames=250, spin_image_size=512,
-			spin_format='gif'):
+			spin_format='gif', surface=False):
 	"""model: a NeuralDisplacementField or a PCAModel whose validation latent tables are indexed by the dataset's item index (batch['idx']);
 	dataset: the validation Foot3DDataset, every foot with keypoints; template_kp_idxs: the template vertices of the keypoints (the
 	template foot's kp_idxs for a neural model, eval_metrics.PCA_KEYPOINTS for a PCAModel; eval_3d.py:132-138).  Ground-truth keypoints
@@ -86,7 +86,10 @@ def eval_3d(model, dataset, template_kp_idxs, samples=10000, z_cutoff=0.07, feet
 	taken on -- and in grey (TexturesVertex(0.5)); each spin is written as it is made.  spin_format: an extension vis.turntable writes
 	('gif', 'png', 'webp', 'npy'; 'mp4' with imageio -- upstream's format).  Either adds to the second dict 'files', the paths written, and
 	produce_spins also 'pred_vertex_error' (N,V) and 'gt_vertex_error', a list of (Vg,) tensors (squared distances).  The metrics do not
-	depend on these keywords: no random number is drawn for them."""
+	depend on these keywords: no random number is drawn for them.
+	surface (not in the reference): eval_metrics.eval_3d_metrics(surface=True) -- 'Scan→pred (mm)', 'Pred→scan (mm)' and 'Surf (μm)' join the
+	returned metrics, with return_per_foot the second dict also holds 'scan_to_pred_mm' and 'pred_to_scan_mm' (N), and the heat maps of
+	produce_spins are coloured from vis.surface_errors (distances to the other surface) instead of vis.vertex_errors."""
 	if (produce_spins or export_meshes) and out_dir is None:
 		raise ValueError('find_amd.evaluate.eval_3d: produce_spins / export_meshes need out_dir')
 	keep_meshes = produce_spins or export_meshes
@@ -125,34 +128,40 @@ def eval_3d(model, dataset, template_kp_idxs, samples=10000, z_cutoff=0.07, feet
 			gt_kps = torch.cat(gt_kps)
 			pred_verts = torch.cat(pred_verts)
 			gt_all = Meshes(gt_v, gt_f)
-			metrics, (_, pred_pts) = eval_3d_metrics(Meshes(pred_v, pred_f), gt_all, pred_verts=pred_verts, template_kp_idxs=kp_t, gt_kps=gt_kps,
-													 samples=samples, z_cutoff=z_cutoff, return_samples=True)
+			pred_all = Meshes(pred_v, pred_f)
+			got = eval_3d_metrics(pred_all, gt_all, pred_verts=pred_verts, template_kp_idxs=kp_t, gt_kps=gt_kps, samples=samples, z_cutoff=z_cutoff,
+								  return_samples=True, **(dict(surface=True, return_per_foot=True) if surface else {}))
+			metrics, (_, pred_pts) = got[0], got[1]
+			surf_per_foot = got[2] if surface else {}
 			per_foot = torch.norm(pred_verts[:, kp_t] - gt_kps, dim=-1) * 1e3
 			written = {}
 			if produce_spins:
-				written = _spins(gt_meshes, pred_meshes, gt_all, pred_verts, pred_pts, os.path.join(out_dir, 'spins'), spin_frames, spin_image_size, spin_format)
+				written = _spins(gt_meshes, pred_meshes, gt_all, pred_verts, pred_pts, os.path.join(out_dir, 'spins'), spin_frames, spin_image_size, spin_format,
+								 pred_all if surface else None)
 			if export_meshes:
 				written.setdefault('files', []).extend(_export(gt_meshes, pred_meshes, os.path.join(out_dir, 'meshes')))
 	finally:
 		model.train(was_training)
-	out = {k: float(metrics[k]) for k in ('Keypoint (mm)', f'Chamf z-cutoff {z_cutoff} (μm)', 'Chamf (μm)')}
+	out = {k: float(metrics[k]) for k in ('Keypoint (mm)', f'Chamf z-cutoff {z_cutoff} (μm)', 'Chamf (μm)') + (('Scan→pred (mm)', 'Pred→scan (mm)', 'Surf (μm)') if surface else ())}
 	if not (return_per_foot or render_correspondences or keep_meshes):
 		return out
 	extra = dict(written)
 	if return_per_foot:
 		extra['keypoint_mm'] = per_foot
+		if surface:
+			extra['scan_to_pred_mm'], extra['pred_to_scan_mm'] = surf_per_foot['Scan→pred (mm)'], surf_per_foot['Pred→scan (mm)']
 	if render_correspondences:
 		extra.update({k: torch.cat(v) for k, v in images.items()})
 	return out, extra
 
 
-def _spins(gt_meshes, pred_meshes, gt_all, pred_verts, pred_pts, spins_dir, nframes, image_size, fmt):
-	"""The six spins per foot of eval_3d.py:163-201; the heat maps of all feet come from one vertex_errors call.  Returns the error tensors and
-	the files written."""
+def _spins(gt_meshes, pred_meshes, gt_all, pred_verts, pred_pts, spins_dir, nframes, image_size, fmt, pred_all=None):
+	"""The six spins per foot of eval_3d.py:163-201; the heat maps of all feet come from one vertex_errors call -- from one surface_errors call
+	when pred_all, the predictions as one batch, is given.  Returns the error tensors and the files written."""
 	from . import vis
 	os.makedirs(spins_dir, exist_ok=True)
 	n_gt = gt_all.num_verts_per_mesh()
-	pred_err, gt_err = vis.vertex_errors(pred_verts, gt_all.verts_padded(), pred_pts, n_gt)
+	pred_err, gt_err = vis.vertex_errors(pred_verts, gt_all.verts_padded(), pred_pts, n_gt) if pred_all is None else vis.surface_errors(pred_all, gt_all)
 	pred_col, gt_col = vis.error_colours(pred_err), vis.error_colours(gt_err)
 	files = []
 	for n, (gt, pred) in enumerate(zip(gt_meshes, pred_meshes)):

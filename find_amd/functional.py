@@ -873,6 +873,61 @@ def sample_surface(verts, faces, rnd, attr=None):
 	return r
 
 
+# ----------------------------------------------------------------------------------------------- point to surface
+class _PointFace(torch.autograd.Function):
+	"""Nearest closed triangle of every point (find_point_face_fwd / _bwd): dist2, and idx and bary as non-differentiable outputs."""
+
+	@staticmethod
+	def forward(ctx, points, verts, faces, p_len):
+		_require_gpu(points, verts)
+		L = _lib.lib()
+		points, verts = _c(points), _c(verts)
+		faces = _faces_i32(faces)
+		if points.dim() != 3 or verts.dim() != 3 or points.shape[-1] != 3 or verts.shape[-1] != 3 or verts.shape[0] != points.shape[0]:
+			raise RuntimeError(f'find_amd.point_face_distance: points (N, P, 3) and verts (N, V, 3) expected, got {tuple(points.shape)} / {tuple(verts.shape)}')
+		N, P, _ = points.shape
+		V = verts.shape[1]
+		if faces.dim() not in (2, 3) or faces.shape[-1] != 3 or (faces.dim() == 3 and faces.shape[0] not in (1, N)):
+			raise RuntimeError(f'find_amd.point_face_distance: faces (F, 3) or ({N}, F, 3) expected, got {tuple(faces.shape)}')
+		fb = 1 if faces.dim() == 2 else faces.shape[0]
+		F = faces.shape[-2]
+		dev = points.device
+		pl = None if p_len is None else torch.as_tensor(p_len).to(device=dev, dtype=torch.int32).contiguous()
+		dist2 = torch.empty(N, P, device=dev, dtype=torch.float32)
+		idx = torch.empty(N, P, device=dev, dtype=torch.int32)
+		bary = torch.empty(N, P, 3, device=dev, dtype=torch.float32)
+		ws = _ws(L.find_point_face_ws_bytes(N, P), dev)
+		check(L.find_point_face_fwd(ptr(points), ptr(pl), ptr(verts), ptr(faces), fb, N, P, V, F, ptr(dist2), ptr(idx), ptr(bary), ptr(ws), ws.numel(),
+									current_stream(dev)), 'find_point_face_fwd')
+		ctx.save_for_backward(points, verts, faces, idx, bary)
+		ctx.dims = (N, P, V, F, fb)
+		ctx.mark_non_differentiable(idx, bary)
+		ctx.set_materialize_grads(False)
+		return dist2, idx, bary
+
+	@staticmethod
+	def backward(ctx, g, _g_idx=None, _g_bary=None):
+		L = _lib.lib()
+		points, verts, faces, idx, bary = ctx.saved_tensors
+		N, P, V, F, fb = ctx.dims
+		need_p, need_v = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+		if g is None or not (need_p or need_v):
+			return None, None, None, None
+		d_points = torch.empty_like(points) if need_p else None
+		d_verts = torch.zeros_like(verts) if need_v else None
+		check(L.find_point_face_bwd(ptr(points), ptr(verts), ptr(faces), fb, ptr(idx), ptr(bary), ptr(_c(g)), N, P, V, F, ptr(d_points), ptr(d_verts),
+									current_stream(points.device)), 'find_point_face_bwd')
+		return d_points, d_verts, None, None
+
+
+def point_face_distance(points, verts, faces, p_len=None):
+	"""Exact point-to-surface distance.  points (N,P,3), verts (N,V,3), faces (F,3) shared or (N,Fmax,3) with -1 rows as padding, p_len (N)
+	point counts or None.  Returns (dist2 (N,P): the squared distance to the nearest closed triangle of mesh n, idx (N,P) int32: that face,
+	bary (N,P,3): the barycentrics of the closest point).  Rows at or past p_len, and a mesh without a face of non-zero area, give 0, -1, 0.
+	Differentiable in points and verts through dist2 (the barycentrics count as constants: the exact gradient almost everywhere)."""
+	return _PointFace.apply(points, verts, faces, p_len)
+
+
 # ----------------------------------------------------------------------------------------------- Chamfer / KNN
 class _NN(torch.autograd.Function):
 	"""dist[n,i] = min_j |x_i - y_j|^2 (K=1 knn_points); gradient flows to both x and the selected y."""

@@ -60,6 +60,18 @@ def chamfer_distance(x, y, x_lengths=None, y_lengths=None):
 	return FN.chamfer_distance(x, y, x_lengths, y_lengths)
 
 
+def _mesh_faces(meshes):
+	faces = meshes.faces_shared()
+	return faces if faces is not None else meshes.faces_padded()
+
+
+def point_mesh_distance(points, meshes: Meshes, lengths=None):
+	"""functional.point_face_distance on a Meshes (shared or ragged, -1 padded faces): (dist2 (N,P), idx (N,P) int32, bary (N,P,3)) of
+	points (N,P,3) against the surface of mesh n; lengths (N): the point counts of a padded batch.  Differentiable in the points and in the
+	meshes' vertices."""
+	return FN.point_face_distance(points, meshes.verts_padded(), _mesh_faces(meshes), lengths)
+
+
 class TextureLossGTSpace(nn.Module):
 	def forward(self, model, batch: dict, num_samples=1000, shapevec=None, texvec=None, posevec=None, gt_samples=None) -> torch.Tensor:
 		"""Sample points + colours on the GT meshes, query the colour field there, masked L2 (reference losses.py:22-57).
@@ -210,3 +222,22 @@ class NormalLoss(nn.Module):
 		"""pred, target (..., 3), not necessarily unit; weight (...) without gradient: sum w (1 - cos) / max(sum w, 1e-12).  The gradient
 		goes to pred only."""
 		return FN.normal_loss(pred, target, weight)
+
+
+class SurfaceDistanceLoss(nn.Module):
+	"""Symmetric point-to-surface distance between predicted and GT meshes (not in the reference, whose Chamfer term measures sample to
+	sample): mean over feet [ mean_i d2(g_i -> predicted mesh) + mean_j d2(s_j -> GT mesh) ], g the surface samples of the scans and s those
+	of the prediction, d2 the exact squared distance to the nearest triangle (functional.point_face_distance).  The same unit as
+	chamfer_distance (m^2), without its floor from the finite sample count."""
+
+	def forward(self, pred_meshes: Meshes, gt_meshes: Meshes, num_samples=5000, gt_samples=None, pred_samples=None):
+		"""gt_samples / pred_samples: (N,S,3) surface samples already drawn (the step's Chamfer samples; pred_samples must carry the sampler's
+		graph for the second term to reach the predicted vertices).  The first term's gradient reaches the predicted vertices through the
+		closest points, the second's through the sampler's backward."""
+		if gt_samples is None:
+			gt_samples = sample_points_from_meshes(gt_meshes, num_samples=num_samples)
+		if pred_samples is None:
+			pred_samples = sample_points_from_meshes(pred_meshes, num_samples=num_samples)
+		to_pred, _, _ = point_mesh_distance(gt_samples.detach(), pred_meshes)
+		to_gt, _, _ = point_mesh_distance(pred_samples, gt_meshes)
+		return (to_pred.mean(1) + to_gt.mean(1)).mean()

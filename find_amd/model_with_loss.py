@@ -13,7 +13,8 @@ import torch
 
 from . import functional as FN
 from . import losses as _losses
-from .losses import ContrastiveLoss, DisplacementLoss, MeshSmoothnessLoss, NormalLoss, RestylePerceptualLoss, SilhouetteLoss, TextureLossGTSpace
+from .losses import (ContrastiveLoss, DisplacementLoss, MeshSmoothnessLoss, NormalLoss, RestylePerceptualLoss, SilhouetteLoss, SurfaceDistanceLoss,
+					 TextureLossGTSpace)
 from .model import NeuralDisplacementField, PCAModel
 from .renderer import FootRenderer
 
@@ -49,6 +50,14 @@ ALL_TERMS = TERMS + ENCODER_TERMS
 EXTENSION_TERMS = (
 	Term('normal', 'loss_normal', 'weight_normal', False, True, '_raw_normal'),
 )
+# ... and the extension terms on the 3-D side, walked last.  p2s: the exact point-to-surface distance between the predicted meshes and the
+# scans (forward(p2s=True)), in the Chamfer term's unit.
+EXTENSION_TERMS_3D = (
+	Term('p2s', 'loss_p2s', 'weight_p2s', True, False, '_raw_p2s'),
+)
+ALL_EXTENSION_TERMS = EXTENSION_TERMS + EXTENSION_TERMS_3D
+# what a reference Opts, which knows nothing of an extension term, is taken to say
+EXTENSION_WEIGHTS = dict(weight_normal=1., weight_p2s=10000.)
 
 
 # the GT render on a second stream beside the predicted one (ModelWithLoss._render_gt); FIND_OVERLAP_GT_RENDER=0 turns it off
@@ -180,6 +189,7 @@ class ModelWithLoss(nn.Module):
 		self.sil_loss = SilhouetteLoss()
 		self.contrastive_loss = ContrastiveLoss()
 		self.normal_loss = NormalLoss()
+		self.surface_loss = SurfaceDistanceLoss()
 		# (max_faces_per_bin only sizes PyTorch3D's coarse bins -- 30 000 for the full-resolution scans, model.py:987; no effect on results)
 		self.rdr = FootRenderer(image_size=256, device=device, bin_size=None, max_faces_per_bin=None if opts.low_poly_meshes else 30000)
 
@@ -225,6 +235,10 @@ class ModelWithLoss(nn.Module):
 		# both maps are the raw world-space blends of the step's shared cameras: the rotation into a view cancels in the dot product and the
 		# loss normalises, so neither goes through normal_map.  A pixel counts by how much both silhouettes cover it; the weight has no gradient.
 		return self.normal_loss(st.pred['normals_raw'], st.gt['normals_raw'], st.gt['mask'] * st.pred['mask'].detach())
+
+	def _raw_p2s(self, st):
+		# (the scans' samples are the Chamfer term's when that term drew them before the main pass)
+		return self.surface_loss(st.res['meshes'], st.batch['mesh'], **(dict(gt_samples=st.gt_chamf) if st.gt_chamf is not None else {}))
 
 	def _raw_pix(self, st):
 		# images are compared inside the silhouettes only (model.py:1101-1105): MSE(image * mask, gt image * gt mask), one pass each way
@@ -318,7 +332,7 @@ class ModelWithLoss(nn.Module):
 	def forward(self, batch, epoch, opts, chamf=False, smooth=False, texture=False, pix=False, vgg_perc=False, sil=False,
 				restyle_perc_lat=False, restyle_perc_feat=False, restyle_perc_cluster=False, cont_pose=False, render_foot=False,
 				save_renders=False, render_dir='_pix', is_train=True, use_z_cutoff=False, gt_z_cutoff=None, restyle_feature_maps=None,
-				no_displacement=False, return_renders=False, copy_mask_out=True, mask_out_pred_faces=False, views=None,
+				no_displacement=False, return_renders=False, copy_mask_out=True, mask_out_pred_faces=False, views=None, p2s=False,
 				cont_pairs=None, normal=False):
 		given = dict(vgg_perc=vgg_perc, restyle_perc_lat=restyle_perc_lat, restyle_perc_feat=restyle_perc_feat, mask_out_pred_faces=mask_out_pred_faces)
 		for name, why in OUT_OF_SCOPE_FLAGS.items():
@@ -342,7 +356,7 @@ class ModelWithLoss(nn.Module):
 			if batch['pose_code'].shape[0] > 1:
 				pairs = cont_pairs if cont_pairs is not None else _losses.pairs_to_device(_losses.draw_pairs(batch['pose_code'].shape[0]), batch[pvec].device)
 		enabled = dict(chamf=chamf, smooth=smooth, texture=texture, cont_pose=pairs is not None, pix=pix, sil=sil,
-					   restyle_perc_cluster=restyle_perc_cluster, normal=normal)
+					   restyle_perc_cluster=restyle_perc_cluster, normal=normal, p2s=p2s)
 
 		st = _Step()
 		st.cont_pairs = pairs
@@ -408,7 +422,7 @@ class ModelWithLoss(nn.Module):
 			st.pred = self._render_pred(st, st.gt, R, T, side, copy_mask_out, images, mask_image=bool(return_renders or save_renders),
 										features=st.res['cpv'] if part else None, **(dict(normals=True) if normal else {}))
 		raw, weights = {}, []
-		active = [t for t in ALL_TERMS + EXTENSION_TERMS if enabled[t.flag] and not (t.needs_3d and not supervise_3d) and not (t.needs_render and not rendering)]
+		active = [t for t in ALL_TERMS + ALL_EXTENSION_TERMS if enabled[t.flag] and not (t.needs_3d and not supervise_3d) and not (t.needs_render and not rendering)]
 		# The Chamfer term -- surface sampling and a brute-force nearest-neighbour search: packed fp32 VALU work, no matrix pipe -- beside the
 		# texture term's MLP pass (matrix pipe) on a second stream: they want different halves of a CU.  Autograd replays each term's
 		# backward on the stream of its forward, so the two backward halves overlap as well.  Not under stream capture.
@@ -459,8 +473,8 @@ class ModelWithLoss(nn.Module):
 				tex_fn._set_sequence_nr(verts_fn._sequence_nr() + 1)
 		for term in active:   # (reported, and summed, in the registry's order whatever the issue order was)
 			raw[term.key] = got[term.key]
-			# (a reference Opts knows nothing of an extension term's weight: 1)
-			weights.append(float(getattr(opts, term.weight, 1.) if term in EXTENSION_TERMS else getattr(opts, term.weight)))
+			# (a reference Opts knows nothing of an extension term's weight: EXTENSION_WEIGHTS)
+			weights.append(float(getattr(opts, term.weight, EXTENSION_WEIGHTS[term.weight]) if term in ALL_EXTENSION_TERMS else getattr(opts, term.weight)))
 		for side in (aside, third, tex_side):
 			if side is not None:
 				torch.cuda.current_stream(dev).wait_stream(side)

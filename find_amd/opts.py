@@ -31,6 +31,8 @@ class Opts:
 		render_dir='_pix',
 		# not in the reference: the surface-normal term (ModelWithLoss.forward(normal=True); passed in model_kwargs, not by net_train_kwargs)
 		normal_loss=False, weight_normal=1.,
+		# not in the reference: the point-to-surface term (ModelWithLoss.forward(p2s=True)); m^2 like the Chamfer term, hence its weight
+		p2s_loss=False, weight_p2s=10000.,
 	)
 
 	def __init__(self, **kw):

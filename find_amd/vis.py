@@ -113,6 +113,16 @@ def vertex_errors(pred_verts, gt_verts, pred_samples, gt_lengths=None):
 	return pred_err, gt_err
 
 
+def surface_errors(pred_meshes, gt_meshes):
+	"""Per-vertex squared distances to the other SURFACE (losses.point_mesh_distance), the exact counterpart of vertex_errors:
+	(pred_err (N,V), gt_err (N,Vg_max)); padded rows are 0."""
+	from .losses import point_mesh_distance
+	with torch.no_grad():
+		pred_err, _, _ = point_mesh_distance(pred_meshes.verts_padded().detach(), gt_meshes, pred_meshes.num_verts_per_mesh())
+		gt_err, _, _ = point_mesh_distance(gt_meshes.verts_padded().detach(), pred_meshes, gt_meshes.num_verts_per_mesh())
+	return pred_err, gt_err
+
+
 def error_colours(err, max_col=MAX_COL):
 	"""(..., 3) heat-map colours of squared distances: red = clamp(err / max_col, 0, 1), green = blue = 0 (eval_3d.py:180-187).  An error of
 	max_col or more is exactly 1 (torch divides by a Python number as a product with its reciprocal, which may fall one ulp short)."""

@@ -220,8 +220,9 @@ int find_linear_wgrad(find_ctx* ctx, const float* dz, const float* x, int64_t n_
  * tests/test_gpu_geom.py compare them): 8 no early exit of finished pixels / tiles, 16 tile lists left in face order (no depth-slab sort),
  * 256 a list pool of 512 entries per image (tiles without room scan the faces themselves); Chamfer: 512 all pairs at every size, 1024 the
  * uniform grid from 64 points per cloud on (geom.hip); 2048 / 4096 the band / the candidate-list rasteriser at every image size (default: the
- * band kernel from 384^2 pixels on, csrc/render_band.h -- the two agree in everything but the last bits of the alpha products).  Any other bit
- * is refused (FIND_EINVAL). */
+ * band kernel from 384^2 pixels on, csrc/render_band.h -- the two agree in everything but the last bits of the alpha products); 8192
+ * find_point_face_fwd never splits a mesh's faces over several workgroups (surface.hip; tests/test_gpu_surface.py).  Any other bit is
+ * refused (FIND_EINVAL). */
 int find_render_switches(int64_t bits);
 /* ------------------------------------------------------------------------------------------------
  * Latent-table lookup.  Replaces LatentVector.__getitem__ with a tensor of indices (src/model/model.py:131-152;
@@ -320,6 +321,26 @@ int64_t find_normal_loss_ws_bytes(int64_t P);
 int find_normal_loss_fwd(const float* pred, const float* target, const float* weight, int64_t P, float* loss_out, void* ws, int64_t ws_bytes, void* stream);
 int find_normal_loss_bwd(const float* pred, const float* target, const float* weight, int64_t P, const float* d_loss, const void* ws, float* d_pred,
 						 void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Exact point-to-surface distance (surface.hip; not in the reference -- PyTorch3D's point_mesh_face_distance is the nearest relative).
+ * points (N, P, 3) with per-mesh counts p_len (N) int32 (NULL = all P); verts (N, V, 3); faces (faces_batch, F, 3) int32, faces_batch 1
+ * (shared) or N (per mesh, rows of -1 pad the shorter ones), as find_face_areas.  P = 0 and F = 0 are allowed.
+ * find_point_face_fwd: for every valid point the nearest CLOSED triangle of its mesh: dist2 (N, P) the squared distance, idx (N, P) int32
+ *   the face, bary (N, P, 3) the barycentrics of the closest point c = sum_i bary_i v_i, with dist2 = |p - c|^2 of those very weights.
+ *   A -1 row, a face with an index outside [0, V) and a face whose float32 (b - a) x (c - a) is exactly zero (products rounded one by one)
+ *   are never candidates; among equal distances the smallest face index wins.  Rows at or past p_len[n], and every row of a mesh without a
+ *   candidate, get dist2 0, idx -1, bary 0.  Brute force over all faces with a bounding-sphere cull, no float atomics: bit-identical on
+ *   repeat.  ws: find_point_face_ws_bytes(N, P) bytes, 8-byte aligned, free again when the call's work is done.
+ * find_point_face_bwd: from g (N, P), the gradient of dist2:  d_points (N, P, 3) = 2 g (p - c), overwritten, every row (0 where idx is -1);
+ *   d_verts[n, faces[idx, i]] += -2 g bary_i (p - c) with float atomics: d_verts (N, V, 3) must be zero-initialised.  The barycentrics count
+ *   as constants (c minimises the distance over the triangle), which is the exact gradient almost everywhere.  Either output may be NULL.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t find_point_face_ws_bytes(int64_t n_meshes, int64_t n_points);
+int find_point_face_fwd(const float* points, const int32_t* p_len, const float* verts, const int32_t* faces, int64_t faces_batch, int64_t n_meshes,
+						int64_t n_points, int64_t n_verts, int64_t n_faces, float* dist2, int32_t* idx, float* bary, void* ws, int64_t ws_bytes, void* stream);
+int find_point_face_bwd(const float* points, const float* verts, const int32_t* faces, int64_t faces_batch, const int32_t* idx, const float* bary,
+						const float* g, int64_t n_meshes, int64_t n_points, int64_t n_verts, int64_t n_faces, float* d_points, float* d_verts, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Similarity registration  X = ((v + disp) * S) @ R(euler 'XYZ') + t.
