@@ -90,6 +90,10 @@ PROTOTYPES = {
 	'find_point_face_ws_bytes': (c_int64, [_I, _I]),
 	'find_point_face_fwd': (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P]),
 	'find_point_face_bwd': (c_int, [_P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
+	'find_depth_bwd': (c_int, [POINTER(RenderParams), _P, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
+	'find_depth_loss_ws_bytes': (c_int64, [_I, _I]),
+	'find_depth_loss_fwd': (c_int, [_P, _P, _P, _I, _I, c_int, c_float, c_float, _P, _P, _P, _I, _P]),
+	'find_depth_loss_bwd': (c_int, [_P, _P, _P, _I, _I, c_int, c_float, c_float, _P, _P, _P, _P]),
 	'find_uv_sample': (c_int, [_P, _I, _I, _I, _P, _I, _P, _I, _I, _P, _P, _I, _I, _P, _P]),
 	'find_render_frags': (c_int, [POINTER(RenderParams), _I, _I, _I, _I, _P, _P, _P, _P]),
 	'find_adam_step': (c_int, [_I, _P, _P, _P, _P, _P, c_float, c_float, c_float, c_float, c_float, _I, _P]),

@@ -155,3 +155,27 @@ def eval_2d_metrics(pred_rdrs, gt_rdrs, batch_size=None):
 	mse = S[:, SQ] / n
 	return {'MSE': mse, 'PSNR_A': _psnr(mse), 'PSNR_B': _psnr(S[:, SQ_EACH] / n), 'PSNR_C': _psnr(S[:, SQ_COMMON] / n),
 			'IOU': (per[..., INTER] / per[..., UNION]).mean(1)}
+
+
+def depth_error_mm(pred_rdrs, gt_rdrs, return_coverage=False):
+	"""Mean absolute depth error per image, millimetres (not in the reference): renders of N feet x M views with return_depth (FootRenderer
+	output dicts; gt_rdrs may carry mask_out_masks, whose pixels do not count).  1000 * sum w |pred - gt| / sum w over the pixels where both
+	maps see a surface -- the per-image sums of functional.depth_loss (kind 'l1', no truncation), float64, N * M values, foot-major; NaN
+	where the two maps share no pixel.  return_coverage: also the share of the GT's own pixels that the prediction covers, per image (NaN
+	where the GT sees nothing): a prediction that misses the scan scores no depth error there, and this says how much that is."""
+	pd, gd = pred_rdrs['depth'], gt_rdrs['depth']
+	if gd.dim() != 4 or pd.shape != gd.shape:
+		raise ValueError(f'find_amd.depth_error_mm: depth maps must be (feet, views, H, W) of one shape, got {tuple(pd.shape)} / {tuple(gd.shape)}')
+	N, M, H, Wd = gd.shape
+	hide = None if gt_rdrs.get('nothing_hidden', False) else gt_rdrs.get('mask_out_masks')
+	weight = None if hide is None else (~hide).float().reshape(N * M, H * Wd)
+	with torch.no_grad():
+		_, per = FN.depth_loss(_f32(pd).detach().reshape(N * M, H * Wd), _f32(gd).detach().reshape(N * M, H * Wd), weight, kind='l1', trunc=0.,
+							   return_per_image=True)
+		nan = torch.full_like(per[:, 0], float('nan'))
+		err = torch.where(per[:, 1] > 0, 1000. * per[:, 0] / per[:, 1].clamp(min=1e-300), nan)
+		if not return_coverage:
+			return err
+		seen = (gd > 0).reshape(N * M, H * Wd)
+		n_gt = (seen if weight is None else seen & (weight > 0)).sum(1).double()
+		return err, torch.where(n_gt > 0, per[:, 1] / n_gt.clamp(min=1), nan)

@@ -14,7 +14,7 @@ import torch
 from torch.utils.data import DataLoader
 
 from .dataset import BatchCollator
-from .eval_metrics import eval_2d_metrics, eval_3d_metrics
+from .eval_metrics import depth_error_mm, eval_2d_metrics, eval_3d_metrics
 from .renderer import FootRenderer
 from .structures import Meshes, TexturesVertex
 
@@ -31,13 +31,16 @@ def _marked_faces(textures):
 	return torch.argwhere(torch.all(fu == vu.shape[0] - 1, dim=-1)).flatten()
 
 
-def eval_2d(model, dataset, image_size=128, nviews=1, batch_size=1, R=None, T=None, feet_per_call=16, return_per_image=False, device='cuda'):
+def eval_2d(model, dataset, image_size=128, nviews=1, batch_size=1, R=None, T=None, feet_per_call=16, return_per_image=False, device='cuda', depth=False):
 	"""model: a NeuralDisplacementField or a PCAModel whose validation latent tables are indexed by the dataset's item index (batch['idx'], as
 	eval_2d.py:28-35 samples them); dataset: the validation Foot3DDataset.  Views: linspace_views(nviews, dist=0.3, elev_min=-90,
 	elev_max=90) unless R, T are given; groups of `batch_size` consecutive views (nviews // batch_size of them per foot, the loop bound of
 	eval_2d.py:86).  Feet are rendered `feet_per_call` at a time; the metrics are per image sums composed in float64, so the result does
 	not depend on that choice.  Returns {'MSE', 'PSNR_A', 'PSNR_B', 'PSNR_C', 'IOU'} as floats, and with return_per_image also the
-	per-group float64 tensors (foot-major, nviews // batch_size groups per foot) as a second dict."""
+	per-group float64 tensors (foot-major, nviews // batch_size groups per foot) as a second dict.
+	depth (not in the reference): two more columns from eval_metrics.depth_error_mm -- 'Depth (mm)', the mean absolute difference of the two
+	rendered depth maps where both see a surface, and 'Depth coverage', the share of the scan's pixels the prediction covers -- as means over
+	the images that have a value; the per-image tensors (one value per foot and view, NaN where there is none) join the second dict."""
 	renderer = FootRenderer(image_size=image_size, device=device)
 	if R is None:
 		R, T = renderer.linspace_views(nviews=nviews, dist=0.3, elev_min=-90, elev_max=90)
@@ -47,7 +50,8 @@ def eval_2d(model, dataset, image_size=128, nviews=1, batch_size=1, R=None, T=No
 	R, T = R[:n_used].to(device), T[:n_used].to(device)
 	collate = BatchCollator(device=device).collate_batches
 	loader = DataLoader(dataset, batch_size=feet_per_call, shuffle=False, collate_fn=lambda items: (collate(items), [_marked_faces(it['textures']) for it in items]))
-	per = {k: [] for k in METRICS}
+	per = {k: [] for k in METRICS + (('Depth (mm)', 'Depth coverage') if depth else ())}
+	more = dict(return_depth=True) if depth else {}
 	was_training = model.training
 	model.eval()
 	try:
@@ -56,14 +60,18 @@ def eval_2d(model, dataset, image_size=128, nviews=1, batch_size=1, R=None, T=No
 				idx = batch['idx'].to(device)
 				batch.update({vec.name: vec[idx] for vec in model.latent_vectors_val})
 				res = model.get_meshes_from_batch(batch, is_train=False)
-				gt_rdrs = renderer(batch['mesh'], R, T, return_mask=True, mask_out_faces=True, masked_faces=marked, return_mask_out_masks=True)
-				pred_rdrs = renderer(res['meshes'], R, T, return_mask=True)
+				gt_rdrs = renderer(batch['mesh'], R, T, return_mask=True, mask_out_faces=True, masked_faces=marked, return_mask_out_masks=True, **more)
+				pred_rdrs = renderer(res['meshes'], R, T, return_mask=True, **more)
 				for k, v in eval_2d_metrics(pred_rdrs, gt_rdrs, batch_size).items():
 					per[k].append(v)
+				if depth:
+					err, cover = depth_error_mm(pred_rdrs, gt_rdrs, return_coverage=True)
+					per['Depth (mm)'].append(err)
+					per['Depth coverage'].append(cover)
 	finally:
 		model.train(was_training)
 	per = {k: torch.cat(v) for k, v in per.items()}
-	out = {k: float(v.mean()) for k, v in per.items()}
+	out = {k: float(v.nanmean() if k.startswith('Depth') else v.mean()) for k, v in per.items()}
 	return (out, per) if return_per_image else out
 
 

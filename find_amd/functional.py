@@ -1423,6 +1423,108 @@ def normal_loss(pred, target, weight):
 	return _NormalLoss.apply(pred, target.detach(), weight.detach())
 
 
+# ----------------------------------------------------------------------------------------------- depth
+class _DepthMap(torch.autograd.Function):
+	"""The renderer's z-buffer with a gradient to the vertices (find_depth_bwd); the forward launches nothing."""
+
+	@staticmethod
+	def forward(ctx, verts, faces, R, T, params, pix_to_face, zbuf):
+		ctx.params = params
+		ctx.save_for_backward(verts, faces, R, T, pix_to_face)
+		return zbuf.view_as(zbuf)
+
+	@staticmethod
+	def backward(ctx, g):
+		verts, faces, R, T, p2f = ctx.saved_tensors
+		N, V, _ = verts.shape
+		fb, F = (1, faces.shape[0]) if faces.dim() == 2 else faces.shape[:2]
+		d = torch.empty_like(verts)
+		check(_lib.lib().find_depth_bwd(ctypes.byref(ctx.params), ptr(verts), ptr(faces), fb, ptr(R), ptr(T), N, R.shape[0], V, F, ptr(p2f), ptr(_c(g)),
+										ptr(d), current_stream(verts.device)), 'find_depth_bwd')
+		return d, None, None, None, None, None, None
+
+
+def depth_map(verts, faces, R, T, params, pix_to_face, zbuf):
+	"""The K = 1 z-buffer of a render as a differentiable function of the vertices.  verts (N, V, 3); faces (F, 3) shared or (N, F, 3) with
+	rows of -1 as padding; R (M, 3, 3), T (M, 3); params: the render's (functional_render.make_params); pix_to_face (N, M, H, W) int32 and
+	zbuf (N, M, H, W): what that render returned (view-space z of the nearest face, -1 on the background).  Returns zbuf's values bit for
+	bit; the backward differentiates the intersection of every covered pixel's ray with its face's plane (find_depth_bwd: one launch, float
+	atomics into d verts, so two runs may differ in the last bits).  Holds in split mode (clip_faces=True) too: a clipped triangle lies in
+	its face's plane.  The faces a pixel sees count as constants, as in PyTorch3D's fragments.zbuf."""
+	_require_gpu(verts, R, T, zbuf, pix_to_face)
+	H, W = params.image_h, params.image_w
+	if verts.dim() != 3 or verts.shape[-1] != 3 or faces.dim() not in (2, 3) or faces.shape[-1] != 3 or faces.is_floating_point():
+		raise RuntimeError(f'find_amd.depth_map: verts (N, V, 3) and integer faces (F, 3) or (N, F, 3) expected, got {tuple(verts.shape)} / '
+						   f'{tuple(faces.shape)} {faces.dtype}')
+	N, M = verts.shape[0], R.shape[0]
+	if faces.dim() == 3 and faces.shape[0] not in (1, N):
+		raise RuntimeError(f'find_amd.depth_map: {faces.shape[0]} face lists for {N} meshes')
+	if R.dim() != 3 or tuple(R.shape[1:]) != (3, 3) or tuple(T.shape) != (M, 3):
+		raise RuntimeError(f'find_amd.depth_map: R (M, 3, 3) and T (M, 3) expected, got {tuple(R.shape)} / {tuple(T.shape)}')
+	if tuple(zbuf.shape) != (N, M, H, W) or tuple(pix_to_face.shape) != (N, M, H, W) or pix_to_face.dtype != torch.int32:
+		raise RuntimeError(f'find_amd.depth_map: zbuf and int32 pix_to_face ({N}, {M}, {H}, {W}) expected, got {tuple(zbuf.shape)} / '
+						   f'{tuple(pix_to_face.shape)} {pix_to_face.dtype}')
+	f = _faces_i32(faces)
+	if f.dim() == 3 and f.shape[0] == 1:
+		f = f[0]
+	return _DepthMap.apply(_c(verts), f, _c(R.detach()), _c(T.detach()), params, _c(pix_to_face), zbuf.detach())
+
+
+DEPTH_LOSS_KINDS = dict(l1=0, l2=1, huber=2)   # find_hip.h FIND_DEPTH_*
+
+
+class _DepthLoss(torch.autograd.Function):
+	@staticmethod
+	def forward(ctx, pred, target, weight, kind, delta, trunc, want_per_image):
+		L = _lib.lib()
+		pred, target, weight = _c(pred), _c(target), _c(weight)
+		n_img = pred.shape[0]
+		n_pix = pred.numel() // n_img
+		nbytes = L.find_depth_loss_ws_bytes(n_img, n_pix)
+		if nbytes < 0:
+			check(-1, 'find_depth_loss_ws_bytes')
+		ws = torch.empty((nbytes + 7) // 8, device=pred.device, dtype=torch.float64)   # sum w (read by the backward) and the block partials
+		loss = torch.empty((), device=pred.device, dtype=torch.float32)
+		per_image = torch.empty(n_img, 2, device=pred.device, dtype=torch.float64) if want_per_image else None
+		check(L.find_depth_loss_fwd(ptr(pred), ptr(target), ptr(weight), n_img, n_pix, kind, delta, trunc, ptr(loss), ptr(per_image), ptr(ws),
+									ws.numel() * 8, current_stream(pred.device)), 'find_depth_loss_fwd')
+		ctx.args = (n_img, n_pix, kind, delta, trunc)
+		ctx.save_for_backward(pred, target, weight, ws)
+		if per_image is not None:
+			ctx.mark_non_differentiable(per_image)
+		return loss, per_image
+
+	@staticmethod
+	def backward(ctx, g, _gp):
+		pred, target, weight, ws = ctx.saved_tensors
+		n_img, n_pix, kind, delta, trunc = ctx.args
+		d = torch.empty_like(pred)
+		check(_lib.lib().find_depth_loss_bwd(ptr(pred), ptr(target), ptr(weight), n_img, n_pix, kind, delta, trunc, ptr(_c(g)), ptr(ws), ptr(d),
+											 current_stream(pred.device)), 'find_depth_loss_bwd')
+		return d, None, None, None, None, None, None
+
+
+def depth_loss(pred, target, weight=None, kind='l1', delta=0.005, trunc=0., return_per_image=False):
+	"""Masked, robust loss between two depth maps: pred, target (n_img, ...) -- e.g. (N, M, H, W) folds to N images --, weight of the same
+	shape or None (= 1), without gradient.  With r = pred - target, a pixel is valid where pred > 0, target > 0 (the renderer's background
+	is -1) and |r| <= trunc (trunc <= 0: no limit):
+	    sum_i w_i rho(r_i) / max(sum_i w_i, 1e-12),   w_i = weight_i on valid pixels, 0 elsewhere,
+	rho = |r| ('l1'), r^2 ('l2'), or r^2 / (2 delta) up to |r| = delta and |r| - delta / 2 beyond ('huber').  One pass each way and fixed-order
+	sums in double (find_depth_loss_*): two runs agree bit for bit; no valid pixel gives 0 and a zero gradient.  The gradient goes to pred
+	only.  return_per_image: also (n_img, 2) float64 [sum w rho, sum w] per image of the first dimension (eval_metrics.depth_error_mm)."""
+	if kind not in DEPTH_LOSS_KINDS:
+		raise ValueError(f"find_amd.depth_loss: kind 'l1', 'l2' or 'huber', got {kind!r}")
+	if kind == 'huber' and not delta > 0:
+		raise ValueError(f'find_amd.depth_loss: the Huber loss needs delta > 0, got {delta}')
+	_require_gpu(pred, target, weight)
+	if pred.dim() < 2 or target.shape != pred.shape or (weight is not None and weight.shape != pred.shape) or pred.numel() == 0:
+		raise RuntimeError(f'find_amd.depth_loss: pred, target (and weight) of one shape (n_img, ...) expected, got {tuple(pred.shape)} / '
+						   f'{tuple(target.shape)} / {None if weight is None else tuple(weight.shape)}')
+	loss, per_image = _DepthLoss.apply(pred, target.detach(), None if weight is None else weight.detach(), DEPTH_LOSS_KINDS[kind], float(delta),
+									   float(trunc), bool(return_per_image))
+	return (loss, per_image) if return_per_image else loss
+
+
 # Default arithmetic of the 256 -> 256 layers: 'bf16x3' (fp32-faithful on the bf16 matrix pipe; set_mlp_precision below says what that is);
 # FIND_MLP_PRECISION=fp32 selects the fp32 MFMA kernels (A/B runs, the bench's comparison record)
 _MLP_PRECISION = _os.environ.get('FIND_MLP_PRECISION', 'bf16x3')

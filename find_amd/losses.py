@@ -241,3 +241,21 @@ class SurfaceDistanceLoss(nn.Module):
 		to_pred, _, _ = point_mesh_distance(gt_samples.detach(), pred_meshes)
 		to_gt, _, _ = point_mesh_distance(pred_samples, gt_meshes)
 		return (to_pred.mean(1) + to_gt.mean(1)).mean()
+
+
+class DepthLoss(nn.Module):
+	"""Masked, robust loss between a predicted and a target depth map (not in the reference; fitting to a depth sensor or a structured-light
+	scan): one HIP pass each way (functional.depth_loss)."""
+
+	def __init__(self, kind='l1', delta=0.005, trunc=0.):
+		"""kind 'l1' | 'l2' | 'huber' (delta: where it turns linear, metres); trunc > 0: pixels whose depths differ by more -- occlusion
+		edges, where one map sees the far side -- are left out."""
+		super().__init__()
+		if kind not in FN.DEPTH_LOSS_KINDS:
+			raise ValueError(f"DepthLoss: kind 'l1', 'l2' or 'huber', got {kind!r}")
+		self.kind, self.delta, self.trunc = kind, float(delta), float(trunc)
+
+	def forward(self, pred, target, weight=None):
+		"""pred, target (n_img, ...), positive where a surface is seen; weight of the same shape or None, without gradient:
+		sum w rho(pred - target) / max(sum w, 1e-12) over the pixels valid in both maps.  The gradient goes to pred only."""
+		return FN.depth_loss(pred, target, weight, kind=self.kind, delta=self.delta, trunc=self.trunc)

@@ -56,8 +56,16 @@ EXTENSION_TERMS_3D = (
 	Term('p2s', 'loss_p2s', 'weight_p2s', True, False, '_raw_p2s'),
 )
 ALL_EXTENSION_TERMS = EXTENSION_TERMS + EXTENSION_TERMS_3D
-# what a reference Opts, which knows nothing of an extension term, is taken to say
-EXTENSION_WEIGHTS = dict(weight_normal=1., weight_p2s=10000.)
+# ... and, walked after those, the depth term: a masked, robust loss between the rendered depth of the prediction and of the GT scans
+# (forward(depth=True)).  A tuple of its own: the two above are pinned by tests/test_normals_host.py and tests/test_surface_host.py.
+EXTENSION_TERMS_DEPTH = (
+	Term('depth', 'loss_depth', 'weight_depth', False, True, '_raw_depth'),
+)
+EVERY_EXTENSION_TERM = ALL_EXTENSION_TERMS + EXTENSION_TERMS_DEPTH
+# what a reference Opts, which knows nothing of an extension term, is taken to say (weight_depth is not tuned: about a millimetre of mean
+# error against a silhouette MSE of 1e-2)
+EXTENSION_WEIGHTS = dict(weight_normal=1., weight_p2s=10000., weight_depth=100.)
+DEPTH_DEFAULTS = dict(depth_loss_kind='l1', depth_loss_delta=0.005, depth_trunc=0.02)
 
 
 # the GT render on a second stream beside the predicted one (ModelWithLoss._render_gt); FIND_OVERLAP_GT_RENDER=0 turns it off
@@ -160,7 +168,7 @@ def model_from_opts(opts):
 
 class _Step:
 	"""What one forward() call has at hand while the registry is walked."""
-	__slots__ = ('batch', 'epoch', 'opts', 'res', 'is_train', 'use_z_cutoff', 'gt_z_cutoff', 'pred', 'gt', 'gt_chamf', 'gt_tex', 'cont_pairs', 'restyle_feature_maps', 'encodings')
+	__slots__ = ('batch', 'epoch', 'opts', 'res', 'is_train', 'use_z_cutoff', 'gt_z_cutoff', 'pred', 'gt', 'gt_chamf', 'gt_tex', 'cont_pairs', 'restyle_feature_maps', 'encodings', 'copy_mask_out')
 
 
 class ModelWithLoss(nn.Module):
@@ -240,6 +248,21 @@ class ModelWithLoss(nn.Module):
 		# (the scans' samples are the Chamfer term's when that term drew them before the main pass)
 		return self.surface_loss(st.res['meshes'], st.batch['mesh'], **(dict(gt_samples=st.gt_chamf) if st.gt_chamf is not None else {}))
 
+	def _raw_depth(self, st):
+		# The two z-buffers of the step's shared cameras, metres.  The loss leaves out what either map calls background (-1) and, with
+		# opts.depth_trunc, the pixels where one map sees another part of the foot; what the GT's slicing plane hides counts for nothing either
+		# (the weight, without gradient).  The silhouette term owns the rim: no soft depth across occlusion edges.
+		o = {k: getattr(st.opts, k, v) for k, v in DEPTH_DEFAULTS.items()}
+		weight = None
+		if st.copy_mask_out and not st.gt.get('nothing_hidden', False):
+			weight = (~st.gt['mask_out_masks']).float()
+		N, M, H, W = st.gt['depth'].shape
+
+		def fold(t):
+			return None if t is None else t.reshape(N * M, H * W)
+		return FN.depth_loss(fold(st.pred['depth']), fold(st.gt['depth']), fold(weight), kind=o['depth_loss_kind'], delta=o['depth_loss_delta'],
+							 trunc=o['depth_trunc'])
+
 	def _raw_pix(self, st):
 		# images are compared inside the silhouettes only (model.py:1101-1105): MSE(image * mask, gt image * gt mask), one pass each way
 		# (find_image_mse_*; CPU tensors raise there: no fallback)
@@ -271,7 +294,7 @@ class ModelWithLoss(nn.Module):
 			return False
 		return True
 
-	def _render_gt(self, st, views, masked_faces, images=True, normals=False):
+	def _render_gt(self, st, views, masked_faces, images=True, normals=False, depth=False):
 		"""The GT render of a step: (gt, R, T, second stream or None).  It carries no gradient and reads nothing of the prediction, so it
 		runs on a second stream beside the predicted render: C3 step 8.3 -> 7.8 ms (the two rasteriser launches share the chip
 		5 % better than they use it alone, and the predicted render's small launches run under the GT render's tail).  (Issued before the
@@ -290,13 +313,15 @@ class ModelWithLoss(nn.Module):
 			# the GT scans are rendered again every step, as the reference does (model.py:1073-1075)
 			# (normals: the scans' vertex normals as three feature channels of the same raster pass -- gt['normals_raw'], the raw blend)
 			feat = dict(return_features=True, features=st.batch['mesh'].verts_normals_padded()) if normals else {}
+			if depth:   # (gt['depth']: the K = 1 z-buffer of the same raster pass)
+				feat['return_depth'] = True
 			gt = self.rdr(st.batch['mesh'], R, T, return_images=images, return_mask=True, mask_with_grad=True, mask_out_faces=True,
 						  masked_faces=masked_faces, return_mask_out_masks=True, **feat)
 			if normals:
 				gt['normals_raw'] = gt.pop('features')
 		return gt, R, T, side
 
-	def _render_pred(self, st, gt, R, T, side, copy_mask_out, images=True, mask_image=True, features=None, normals=False):
+	def _render_pred(self, st, gt, R, T, side, copy_mask_out, images=True, mask_image=True, features=None, normals=False, depth=False):
 		# features: per-vertex class logits (1, V, C) rendered beside the mask (model.py:1077-1081), shared by the N feet -- upstream hands
 		# the renderer the (1, V, C) tensor, which only works at N = 1; the expansion's backward sums over the feet
 		# normals: the predicted meshes' vertex normals as the first three feature channels of the same raster pass (pred['normals_raw'])
@@ -304,6 +329,8 @@ class ModelWithLoss(nn.Module):
 		if features is not None:
 			chans.append(features.expand(len(st.res['meshes']), -1, -1))
 		feat = {} if not chans else dict(return_features=True, features=chans[0] if len(chans) == 1 else torch.cat(chans, dim=-1))
+		if depth:   # (pred['depth']: the z-buffer, differentiable to the vertices through functional.depth_map)
+			feat['return_depth'] = True
 		pred = self.rdr(st.res['meshes'], R, T, return_images=images, return_mask=True, mask_with_grad=True, **feat)
 		if normals:
 			both = pred.pop('features')
@@ -333,7 +360,7 @@ class ModelWithLoss(nn.Module):
 				restyle_perc_lat=False, restyle_perc_feat=False, restyle_perc_cluster=False, cont_pose=False, render_foot=False,
 				save_renders=False, render_dir='_pix', is_train=True, use_z_cutoff=False, gt_z_cutoff=None, restyle_feature_maps=None,
 				no_displacement=False, return_renders=False, copy_mask_out=True, mask_out_pred_faces=False, views=None, p2s=False,
-				cont_pairs=None, normal=False):
+				depth=False, cont_pairs=None, normal=False):
 		given = dict(vgg_perc=vgg_perc, restyle_perc_lat=restyle_perc_lat, restyle_perc_feat=restyle_perc_feat, mask_out_pred_faces=mask_out_pred_faces)
 		for name, why in OUT_OF_SCOPE_FLAGS.items():
 			if given[name]:
@@ -356,10 +383,11 @@ class ModelWithLoss(nn.Module):
 			if batch['pose_code'].shape[0] > 1:
 				pairs = cont_pairs if cont_pairs is not None else _losses.pairs_to_device(_losses.draw_pairs(batch['pose_code'].shape[0]), batch[pvec].device)
 		enabled = dict(chamf=chamf, smooth=smooth, texture=texture, cont_pose=pairs is not None, pix=pix, sil=sil,
-					   restyle_perc_cluster=restyle_perc_cluster, normal=normal, p2s=p2s)
+					   restyle_perc_cluster=restyle_perc_cluster, normal=normal, p2s=p2s, depth=depth)
 
 		st = _Step()
 		st.cont_pairs = pairs
+		st.copy_mask_out = copy_mask_out
 		st.restyle_feature_maps = restyle_feature_maps
 		st.encodings = {} if return_renders else None   # (a dictionary: the part loss is asked for its encodings, model.py:1143-1147)
 		st.batch, st.epoch, st.opts, st.is_train = batch, epoch, opts, is_train
@@ -414,15 +442,17 @@ class ModelWithLoss(nn.Module):
 					t.record_stream(main)
 		st.pred = st.gt = None
 		if rendering:
-			st.gt, R, T, side = self._render_gt(st, views, batch.get('masked_faces', None), images, **(dict(normals=True) if normal else {}))
+			st.gt, R, T, side = self._render_gt(st, views, batch.get('masked_faces', None), images, **(dict(normals=True) if normal else {}),
+												**(dict(depth=True) if depth else {}))
 			part = rendering and restyle_perc_cluster
 			if part and 'cpv' not in st.res:
 				raise ValueError("restyle_perc_cluster with restyle_cluster_per_vertex renders res['cpv'], and the model has no per-vertex "
 								 'classes: set opts.template_features_pth')
 			st.pred = self._render_pred(st, st.gt, R, T, side, copy_mask_out, images, mask_image=bool(return_renders or save_renders),
-										features=st.res['cpv'] if part else None, **(dict(normals=True) if normal else {}))
+										features=st.res['cpv'] if part else None, **(dict(normals=True) if normal else {}),
+										**(dict(depth=True) if depth else {}))
 		raw, weights = {}, []
-		active = [t for t in ALL_TERMS + ALL_EXTENSION_TERMS if enabled[t.flag] and not (t.needs_3d and not supervise_3d) and not (t.needs_render and not rendering)]
+		active = [t for t in ALL_TERMS + EVERY_EXTENSION_TERM if enabled[t.flag] and not (t.needs_3d and not supervise_3d) and not (t.needs_render and not rendering)]
 		# The Chamfer term -- surface sampling and a brute-force nearest-neighbour search: packed fp32 VALU work, no matrix pipe -- beside the
 		# texture term's MLP pass (matrix pipe) on a second stream: they want different halves of a CU.  Autograd replays each term's
 		# backward on the stream of its forward, so the two backward halves overlap as well.  Not under stream capture.
@@ -474,7 +504,7 @@ class ModelWithLoss(nn.Module):
 		for term in active:   # (reported, and summed, in the registry's order whatever the issue order was)
 			raw[term.key] = got[term.key]
 			# (a reference Opts knows nothing of an extension term's weight: EXTENSION_WEIGHTS)
-			weights.append(float(getattr(opts, term.weight, EXTENSION_WEIGHTS[term.weight]) if term in ALL_EXTENSION_TERMS else getattr(opts, term.weight)))
+			weights.append(float(getattr(opts, term.weight, EXTENSION_WEIGHTS[term.weight]) if term in EVERY_EXTENSION_TERM else getattr(opts, term.weight)))
 		for side in (aside, third, tex_side):
 			if side is not None:
 				torch.cuda.current_stream(dev).wait_stream(side)

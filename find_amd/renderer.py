@@ -99,7 +99,10 @@ class FootRenderer(nn.Module):
 		(normals_space='view': n_world @ R[view]) or in world space ('world'), 0 on the background and where mask_out_faces hides a pixel:
 		functional.normal_map of the feature render of the mesh's vertex normals (Meshes.verts_normals_padded), so differentiable to the
 		vertices through the normals and through the blend.  Together with return_features the normals are a feature render of their own
-		on a second raster pass: each output is what the call that asks for it alone returns.  Not in split mode either."""
+		on a second raster pass: each output is what the call that asks for it alone returns.  Not in split mode either.
+		return_depth: out['depth'] (N,M,H,W), view-space z of the nearest face, -1 on the background.  Where gradients are enabled and the
+		vertices require one it is differentiable to them (functional.depth_map; PyTorch3D's fragments.zbuf), in split mode too; the values
+		are the same either way.  UV-textured scans stay without gradient."""
 		if keypoints is not None:
 			if keypoints_blend and not return_images:   # (a NameError upstream)
 				raise ValueError('FootRenderer: keypoints_blend draws the keypoints over the image: it needs return_images=True')
@@ -164,7 +167,9 @@ class FootRenderer(nn.Module):
 															  features=vnormals)[4]
 		out = dict()
 		if return_depth:
-			out['depth'] = zbuf
+			# (with a gradient to carry, the z-buffer goes through functional.depth_map: the same values, and find_depth_bwd behind them)
+			with_grad = torch.is_grad_enabled() and verts.requires_grad and not (return_images and uv_tex)
+			out['depth'] = FN.depth_map(verts, faces, R, T, self.params, p2f, zbuf) if with_grad else zbuf
 		if return_mask and not want_soft:  # hard mask from the image render (renderer.py:313)
 			mask = torch.any(renders < 1, dim=-1).float()
 

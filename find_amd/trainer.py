@@ -128,6 +128,9 @@ class Trainer:
 		if model_kwargs.get('p2s'):
 			return ('the p2s term (the point-to-surface distance, functional.point_face_distance) allocates its workspace and outputs per call and '
 					'has not been taken through a capture')
+		if model_kwargs.get('depth'):
+			return ('the depth term (functional.depth_map, functional.depth_loss) allocates its workspace and outputs per call and has not been taken '
+					'through a capture')
 		if not any(model_kwargs.get(k) for k in ('chamf', 'smooth', 'texture', 'cont_pose', 'pix', 'sil')):
 			return 'no loss term enabled'
 		for op in optims:

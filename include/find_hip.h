@@ -633,6 +633,39 @@ int find_render_features_bwd(const find_render_params* rp, const float* verts, c
 							 int64_t ws_bytes, void* fws, int64_t fws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Depth (depth.hip): the backward of find_render_fwd's zbuf -- view-space z of the nearest face, -1 on the background -- and a masked,
+ * robust loss between two depth maps.  Not in the reference (PyTorch3D's fragments.zbuf carries this gradient).
+ * find_depth_bwd: d_verts (n_meshes, n_verts, 3) is OVERWRITTEN from d_depth (n_meshes, n_views, H, W).  pix_to_face is what
+ *   find_render_fwd handed out: the packed id image * n_faces + f, or -1; verts, faces, faces_batch, R, T as there (faces shared, or per
+ *   mesh with rows of -1 padding).  Self-contained: no render workspace is read.  Per pixel with a face, with p_k = v_k @ R[view] + T[view]
+ *   the face's corners in view space, d = (x_ndc / s, y_ndc / s, 1) the pixel's ray (s = 1 / tan(fov / 2), x_ndc = 1 - (2 xi + 1) / W,
+ *   y_ndc = 1 - (2 yi + 1) / H), n = (p1 - p0) x (p2 - p0):
+ *     z = (n . p0) / (n . d),  X = z d,  b_k = ((p_{k+1} - X) x (p_{k+2} - X)) . n / (n . n),
+ *     d p_k = g b_k n / (n . d),  d v_k += d p_k @ R[view]^T.
+ *   The triangles split mode (clip_faces = 1) cuts lie in their face's plane and pix_to_face names the face: the same formula holds there.
+ *   A pixel with -1, a face index outside [0, n_faces), a vertex index outside [0, n_verts) or n . d == 0 adds nothing and nothing is read
+ *   through such an index.  The sum over pixels uses float atomics: two runs may differ in the last bits.
+ * find_depth_loss_fwd: pred, target (n_img, n_pix); weight (n_img, n_pix) or NULL (= 1).  r = pred - target; a pixel is valid where
+ *   pred > 0, target > 0 and (trunc <= 0 or |r| <= trunc); w_i = weight_i on valid pixels, 0 elsewhere;
+ *   rho = |r| (FIND_DEPTH_L1), r^2 (FIND_DEPTH_L2), r^2 / (2 delta) for |r| <= delta and |r| - delta / 2 beyond (FIND_DEPTH_HUBER, delta > 0);
+ *   *loss_out = sum_i w_i rho(r_i) / max(sum_i w_i, 1e-12).  fp32 per pixel; both sums in double, one pair of partials per workgroup of 1024
+ *   pixels of ONE image, added by one workgroup in a fixed order (no atomics: bit-identical on repeat).  per_image (n_img, 2) fp64 or NULL:
+ *   [sum w rho, sum w] of every image.  16-byte loads and stores where the pointers and the image's first pixel are 16-byte aligned.
+ *   ws: find_depth_loss_ws_bytes(n_img, n_pix) bytes (-1 for bad sizes), 8-byte aligned; the backward reads sum w from it.
+ * find_depth_loss_bwd: d_pred_i = *d_loss w_i rho'(r_i) / max(sum w, 1e-12), overwritten, every element (sign(0) = 0).  target and weight
+ *   receive no gradient.
+ * ---------------------------------------------------------------------------------------------- */
+enum { FIND_DEPTH_L1 = 0, FIND_DEPTH_L2 = 1, FIND_DEPTH_HUBER = 2 };
+int find_depth_bwd(const find_render_params* rp, const float* verts, const int32_t* faces, int64_t faces_batch, const float* R, const float* T,
+				   int64_t n_meshes, int64_t n_views, int64_t n_verts, int64_t n_faces, const int32_t* pix_to_face, const float* d_depth,
+				   float* d_verts, void* stream);
+int64_t find_depth_loss_ws_bytes(int64_t n_img, int64_t n_pix);
+int find_depth_loss_fwd(const float* pred, const float* target, const float* weight, int64_t n_img, int64_t n_pix, int kind, float delta, float trunc,
+						float* loss_out, double* per_image, void* ws, int64_t ws_bytes, void* stream);
+int find_depth_loss_bwd(const float* pred, const float* target, const float* weight, int64_t n_img, int64_t n_pix, int kind, float delta, float trunc,
+						const float* d_loss, const void* ws, float* d_pred, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Fused multi-tensor optimiser steps.  Replace torch.optim.Adam / torch.optim.SGD(momentum=0.9)
  * as constructed by the reference (src/train/train.py:161-168) and stepped once per batch
  * (src/train/trainer.py:121-123).  `param`, `grad`, moment arrays: HOST arrays of n_tensors DEVICE pointers (fp32,
