@@ -1027,6 +1027,401 @@ __global__ __launch_bounds__(256) void nn_grid_query_kernel(const GridQueryArgs 
 	kout[qi] = best;
 }
 
+// ------------------------------------------------------------------------------------------------ nearest neighbour through balanced tiles
+// Between all pairs and the grid: at the training sizes (16 feet x 5000 samples) nearly all of nn_kernel's pairs lie on opposite sides of
+// a foot, and the grid's per-lane dependent loads fare badly beside the MLP chain.  Here a cloud is cut ONCE into equal-count, axis-aligned,
+// compact tiles of at most TILE_PTS points (nn_tile_build_kernel); cloud x's tiles are the targets of direction 1 and the query groups of
+// direction 0, and the reverse for y.  A wave of nn_tile_query_kernel owns one query tile (a query per lane) and scans a target tile -- through
+// LDS, wave-uniform broadcast reads, packed arithmetic over PAIRS OF TARGETS, the minimum of eight distances against the running best
+// (4.5 VALU per pair) -- only if the box-to-box lower bound does not exceed the worst running best of its queries.  Tiles are taken in the
+// order of that bound (the nearest first: the worst wave then scans 12 - 13 tiles, not 33 as in index order), so the search ends at the first
+// tile above it.
+//
+// Partition rule: a k-d tree by levels, no recursion.  A node that owns c points and is to become m = ceil(c / 64) leaves splits into
+// floor(m / 2) and ceil(m / 2) leaves with floor(c * mL / m) and the remaining points -- never more than 64 per leaf, 63 - 64 for 5000 points
+// (79 tiles) -- along the widest axis of its box: a 64-bin histogram of that coordinate (integer LDS atomics), the bin in which the running
+// count crosses the left share, and inside that bin the first arrivals (an LDS counter) go left until the share is full.  So the counts are
+// exact whatever the coordinates are -- coincident, collinear, coplanar, NaN --, the cut is sharp to 1/64 of the node's extent, and WHICH
+// points of the cut bin go left is whatever the atomics make it: the tiling differs from run to run, the keys do not (below).  The boxes that
+// steer the cuts are the root's bounding box cut at the bin edges (loose); the boxes the search uses are the exact minimum and maximum of
+// each tile's members (integer atomics on order-preserving bit patterns).
+//
+// EXACT with a strict '>' and no margin.  Per axis the gap between a query tile [qlo, qhi] and a target tile [tlo, thi] is
+// max(0, tlo - qhi, qlo - thi): one rounded subtraction.  For any query q and target t of the two tiles the real difference |q - t| is at
+// least the real gap, and correctly rounded subtraction is monotone, so |fl(q - t)| >= fl(gap) on every axis; multiplication and fma of
+// non-negative operands are monotone too, so nn_dist(q, t) >= lb2 = fma(gz, gz, fma(gy, gy, gx * gx)) -- nn_dist's own three roundings on the
+// gap vector -- bit for bit, also far from the origin.  A tile with lb2 above the largest running best of the wave's queries can neither win
+// nor tie for any of them; a tile with lb2 EQUAL to it can hold a tie with a lower index and is scanned.  The running best only falls, so a
+// tile skipped once stays skipped.
+//
+// Keys: a query's result is the smallest (distance bits << 32 | original index) among the scanned targets, as everywhere.  Tile order is not
+// index order, so nn_kernel's "earliest group of four wins" does not pick the lowest index here.  Instead: the first group to reach the best
+// distance is kept (strict '<'); a group whose minimum EQUALS the running best (duplicated points: rare) takes a branch that folds the keys
+// of its tying targets into a second key; at the end the kept group's eight targets are recomputed with nn_dist and the smallest of their
+// keys and the tie key is the answer (every candidate is a real target of the cloud, the best one is among them, and a tie key from before
+// a strict improvement has a larger distance and loses).
+constexpr int TILE_PTS = 64;
+constexpr int TILE_MAX_TILES = 128;
+constexpr int TILE_MAX_POINTS = TILE_PTS * TILE_MAX_TILES;   // per cloud: eight points per thread of the build, two target tiles per lane of the search
+struct TileDir {
+	const float* p;          // points (n, p_max, 3)
+	const int32_t* len;      // (n) or NULL
+	int p_max;
+	float4* sorted;          // (n, p_max): x, y, z, original index (bits), in tile order
+	float4* tab;             // (n, cdiv(p_max, 64), 2): box minimum xyz + first point (bits), box maximum xyz + number of points (bits)
+};
+struct TileBuildArgs { TileDir d[2]; };
+
+__device__ __forceinline__ unsigned tile_ord(float f) {   // unsigned order == float order (-0 < +0)
+	const unsigned b = __float_as_uint(f);
+	return b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u);
+}
+__device__ __forceinline__ float tile_unord(unsigned u) { return __uint_as_float(u ^ ((u >> 31) ? 0x80000000u : 0xffffffffu)); }
+__device__ __forceinline__ int tile_bin(float v, float lo, float scale) { return (int)fminf(fmaxf((v - lo) * scale, 0.f), 63.f); }   // (NaN -> 0)
+
+// Maximum over the wave of non-negative floats as bit patterns: within rows of 16 by DPP, across the four rows on the scalar unit.
+__device__ __forceinline__ unsigned tile_wave_max(unsigned v) {
+	v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xf, 0xf, true));    // quad_perm 1,0,3,2
+	v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xf, 0xf, true));    // quad_perm 2,3,0,1
+	v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xf, 0xf, true));   // row_half_mirror
+	v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x140, 0xf, 0xf, true));   // row_mirror
+	return max(max((unsigned)__builtin_amdgcn_readlane((int)v, 0), (unsigned)__builtin_amdgcn_readlane((int)v, 16)),
+			   max((unsigned)__builtin_amdgcn_readlane((int)v, 32), (unsigned)__builtin_amdgcn_readlane((int)v, 48)));
+}
+
+// Running sum over the wave (inclusive): within rows of 16 by DPP, the three row totals on the scalar unit.
+__device__ __forceinline__ int tile_wave_scan(int v, int lane) {
+	v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, true);   // row_shr:1
+	v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, true);   // row_shr:2
+	v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, true);   // row_shr:4
+	v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, true);   // row_shr:8
+	const int r0 = __builtin_amdgcn_readlane(v, 15), r1 = __builtin_amdgcn_readlane(v, 31), r2 = __builtin_amdgcn_readlane(v, 47);
+	return v + (lane >= 16 ? r0 : 0) + (lane >= 32 ? r1 : 0) + (lane >= 48 ? r2 : 0);
+}
+__device__ __forceinline__ int tile_widest(float ex, float ey, float ez) {   // (an empty or NaN extent: axis 0)
+	return (ey > ex && ey >= ez) ? 1 : (ez > ex && ez > ey) ? 2 : 0;
+}
+
+// Two barriers per level: [a wave per node: where to cut, the two children] | [every point to its child, and into the child's histogram].
+// What a point reads of a node is packed into one 16-byte LDS word per phase, and the phases run over a thread's points in stages (all
+// reads, then all atomics, ...), so that the LDS latencies of a thread's points overlap instead of adding up.
+__global__ __launch_bounds__(1024) void nn_tile_build_kernel(const TileBuildArgs a) {
+	constexpr int PPT = TILE_MAX_POINTS / 1024, MT = TILE_MAX_TILES;
+	__shared__ int hist[MT / 2 * 64];        // of a splitting node (two leaves or more: first leaves at least two apart), at (first leaf / 2)
+	__shared__ int n_m[2][MT];               // nodes of a level, at their first leaf: leaves below (0: no node starts here); by level parity
+	__shared__ int n_cnt[MT], n_start[MT], n_axis[MT];
+	__shared__ float n_lo[3][MT], n_hi[3][MT];
+	__shared__ float4 n_par[MT];             // for the points of a node: leaves below (bits), axis (bits), box minimum along it, 64 / extent
+	__shared__ int4 s_split[MT];             // the split of a level: leaves that go left (0: a leaf already), cut bin, how many of that bin go left
+	__shared__ int s_taken[MT];
+	__shared__ unsigned b_lo[3][MT], b_hi[3][MT];
+	__shared__ unsigned red[6][16];
+	const int dir = blockIdx.y, n = blockIdx.x;
+	const float* __restrict__ pts = dir ? a.d[1].p : a.d[0].p;
+	const int32_t* len = dir ? a.d[1].len : a.d[0].len;
+	const int p_max = dir ? a.d[1].p_max : a.d[0].p_max;
+	const int p = min(max(len ? len[n] : p_max, 0), p_max);
+	const int M = (p + TILE_PTS - 1) / TILE_PTS;
+	if (M == 0 || M > MT) return;   // (the host never launches this for larger clouds)
+	float4* sorted = (dir ? a.d[1].sorted : a.d[0].sorted) + (int64_t)n * p_max;
+	float4* tab = (dir ? a.d[1].tab : a.d[0].tab) + (int64_t)n * ((p_max + TILE_PTS - 1) / TILE_PTS) * 2;
+	const float* pp = pts + (int64_t)n * p_max * 3;
+	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+	const int kmax = (p + 1023) >> 10;   // points per thread that exist: the stages below skip the rest
+	float px[PPT], py[PPT], pz[PPT];
+	int node[PPT], bin[PPT];
+	bool own[PPT];
+	float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+#pragma unroll
+	for (int k = 0; k < PPT; ++k) {
+		const int j = k * 1024 + tid;
+		own[k] = j < p;
+		node[k] = 0;
+		bin[k] = 0;
+		const int jj = min(j, p - 1);
+		px[k] = pp[(int64_t)jj * 3]; py[k] = pp[(int64_t)jj * 3 + 1]; pz[k] = pp[(int64_t)jj * 3 + 2];
+		lo[0] = fminf(lo[0], px[k]); hi[0] = fmaxf(hi[0], px[k]);
+		lo[1] = fminf(lo[1], py[k]); hi[1] = fmaxf(hi[1], py[k]);
+		lo[2] = fminf(lo[2], pz[k]); hi[2] = fmaxf(hi[2], pz[k]);
+	}
+	// the root's box: minima as maxima of the complemented order-preserving bit patterns
+#pragma unroll
+	for (int c = 0; c < 3; ++c) {
+		const unsigned l = tile_wave_max(~tile_ord(lo[c])), h = tile_wave_max(tile_ord(hi[c]));
+		if (lane == 0) { red[c][wave] = l; red[3 + c][wave] = h; }
+	}
+	for (int i = tid; i < MT / 2 * 64; i += 1024) hist[i] = 0;
+	if (tid < MT) {
+		n_m[0][tid] = 0; n_m[1][tid] = 0; s_taken[tid] = 0;
+		s_split[tid] = make_int4(0, 0, 0, 0);
+#pragma unroll
+		for (int c = 0; c < 3; ++c) { b_lo[c][tid] = 0xffffffffu; b_hi[c][tid] = 0u; }
+	}
+	__syncthreads();
+	// what the points of a node with this box need: (an empty or NaN extent: every point in bin 0, the arrival order splits)
+	auto node_par = [](int m, int ax, float l, float h) {
+		const float e = h - l;
+		return make_float4(__int_as_float(m), __int_as_float(ax), l, e > 0.f ? 64.0f / e : 0.f);
+	};
+	if (tid == 0) {
+		float l[3], h[3];
+		for (int c = 0; c < 3; ++c) {
+			unsigned ul = 0u, uh = 0u;
+			for (int w = 0; w < 16; ++w) { ul = max(ul, red[c][w]); uh = max(uh, red[3 + c][w]); }
+			l[c] = tile_unord(~ul); h[c] = tile_unord(uh);
+			n_lo[c][0] = l[c]; n_hi[c][0] = h[c];
+		}
+		const int ax = tile_widest(h[0] - l[0], h[1] - l[1], h[2] - l[2]);
+		n_m[0][0] = M; n_cnt[0] = p; n_start[0] = 0; n_axis[0] = ax;
+		n_par[0] = node_par(M, ax, l[ax], h[ax]);
+	}
+	__syncthreads();
+	// every point into the 64-bin histogram of its node along the node's axis, if the node still splits
+	auto hist_all = [&]() {
+		float4 np[PPT];
+#pragma unroll
+		for (int k = 0; k < PPT; ++k)
+			if (k < kmax) np[k] = n_par[node[k]];
+#pragma unroll
+		for (int k = 0; k < PPT; ++k) {
+			if (k >= kmax) break;
+			const int ax = __float_as_int(np[k].y);
+			const float v = ax == 0 ? px[k] : ax == 1 ? py[k] : pz[k];
+			bin[k] = tile_bin(v, np[k].z, np[k].w);
+			if (own[k] && __float_as_int(np[k].x) >= 2) atomicAdd(&hist[(node[k] >> 1) * 64 + bin[k]], 1);
+		}
+	};
+	hist_all();
+	__syncthreads();
+	int depth = 0;
+	while ((1 << depth) < M) ++depth;
+	for (int level = 0; level < depth; ++level) {
+		const int cur = level & 1, nxt = cur ^ 1;
+		// ---- a wave per node: the bin in which the running count reaches the left share; the two children
+		for (int f = wave; f < M; f += 16) {
+			const int m = n_m[cur][f];
+			const int hi_ = (f >> 1) * 64 + lane;
+			const int h = hist[hi_];
+			const int cnt = n_cnt[f], start = n_start[f], ax = n_axis[f];
+			const float bl[3] = {n_lo[0][f], n_lo[1][f], n_lo[2][f]}, bh[3] = {n_hi[0][f], n_hi[1][f], n_hi[2][f]};
+			if (m == 0) continue;
+			if (m == 1) {
+				if (lane == 0) { n_m[nxt][f] = 1; s_split[f] = make_int4(0, 0, 0, 0); n_par[f] = make_float4(__int_as_float(1), 0.f, 0.f, 0.f); }
+				continue;
+			}
+			hist[hi_] = 0;   // (clean for whichever node uses the slot next)
+			const int inc = tile_wave_scan(h, lane);
+			const int mL = m >> 1;
+			const int cL = (int)(((int64_t)cnt * mL) / m);
+			const unsigned long long reached = __ballot(inc >= cL);
+			const int sb = reached ? __builtin_ctzll(reached) : 63;
+			const int before = __builtin_amdgcn_readlane(inc - h, sb);
+			const float l = ax == 0 ? bl[0] : ax == 1 ? bl[1] : bl[2], hh = ax == 0 ? bh[0] : ax == 1 ? bh[1] : bh[2];
+			const float e = hh - l, w = e > 0.f ? e * (1.0f / 64.0f) : 0.f;
+			const float cut_l = l + (float)(sb + 1) * w, cut_r = l + (float)sb * w;   // the left child ends / the right child begins here
+			float lh[3] = {bh[0], bh[1], bh[2]}, rl[3] = {bl[0], bl[1], bl[2]};
+#pragma unroll
+			for (int c = 0; c < 3; ++c) { if (c == ax) { lh[c] = cut_l; rl[c] = cut_r; } }
+			const int ax_l = tile_widest(lh[0] - bl[0], lh[1] - bl[1], lh[2] - bl[2]), ax_r = tile_widest(bh[0] - rl[0], bh[1] - rl[1], bh[2] - rl[2]);
+			if (lane == 0) {
+				const int r = f + mL;
+				s_split[f] = make_int4(mL, sb, cL - before, 0); s_taken[f] = 0;
+#pragma unroll
+				for (int c = 0; c < 3; ++c) { n_hi[c][f] = lh[c]; n_lo[c][r] = rl[c]; n_hi[c][r] = bh[c]; }
+				n_m[nxt][f] = mL; n_cnt[f] = cL; n_axis[f] = ax_l;
+				n_m[nxt][r] = m - mL; n_cnt[r] = cnt - cL; n_start[r] = start + cL; n_axis[r] = ax_r;
+				n_par[f] = node_par(mL, ax_l, ax_l == 0 ? bl[0] : ax_l == 1 ? bl[1] : bl[2], ax_l == 0 ? lh[0] : ax_l == 1 ? lh[1] : lh[2]);
+				n_par[r] = node_par(m - mL, ax_r, ax_r == 0 ? rl[0] : ax_r == 1 ? rl[1] : rl[2], ax_r == 0 ? bh[0] : ax_r == 1 ? bh[1] : bh[2]);
+			}
+		}
+		__syncthreads();
+		// ---- every point to its child, and into the child's histogram
+		if (tid < MT) n_m[cur][tid] = 0;
+		int4 sp[PPT];
+		int arrived[PPT];
+#pragma unroll
+		for (int k = 0; k < PPT; ++k)
+			if (k < kmax) sp[k] = s_split[node[k]];
+#pragma unroll
+		for (int k = 0; k < PPT; ++k) {
+			arrived[k] = 0;
+			if (k < kmax && own[k] && sp[k].x != 0 && bin[k] == sp[k].y) arrived[k] = atomicAdd(&s_taken[node[k]], 1);
+		}
+#pragma unroll
+		for (int k = 0; k < PPT; ++k) {
+			if (k >= kmax) break;
+			const bool left = bin[k] < sp[k].y || (bin[k] == sp[k].y && arrived[k] < sp[k].z);
+			if (sp[k].x != 0 && !left) node[k] += sp[k].x;
+		}
+		hist_all();
+		__syncthreads();
+	}
+	// ---- scatter into tile order; the exact box of every tile
+	if (tid < MT) s_taken[tid] = 0;
+	__syncthreads();
+	int pos[PPT];
+#pragma unroll
+	for (int k = 0; k < PPT; ++k) pos[k] = own[k] ? n_start[node[k]] + atomicAdd(&s_taken[node[k]], 1) : -1;
+#pragma unroll
+	for (int k = 0; k < PPT; ++k) {
+		if (!own[k]) continue;
+		const int f = node[k];
+		atomicMin(&b_lo[0][f], tile_ord(px[k])); atomicMax(&b_hi[0][f], tile_ord(px[k]));
+		atomicMin(&b_lo[1][f], tile_ord(py[k])); atomicMax(&b_hi[1][f], tile_ord(py[k]));
+		atomicMin(&b_lo[2][f], tile_ord(pz[k])); atomicMax(&b_hi[2][f], tile_ord(pz[k]));
+	}
+#pragma unroll
+	for (int k = 0; k < PPT; ++k)
+		if (pos[k] >= 0 && pos[k] < p) sorted[pos[k]] = make_float4(px[k], py[k], pz[k], __int_as_float(k * 1024 + tid));
+	__syncthreads();
+	if (tid < M) {
+		tab[2 * tid] = make_float4(tile_unord(b_lo[0][tid]), tile_unord(b_lo[1][tid]), tile_unord(b_lo[2][tid]), __int_as_float(n_start[tid]));
+		tab[2 * tid + 1] = make_float4(tile_unord(b_hi[0][tid]), tile_unord(b_hi[1][tid]), tile_unord(b_hi[2][tid]), __int_as_float(n_cnt[tid]));
+	}
+}
+
+struct TileQueryDir {
+	const float4* qsorted;   // the query cloud in tile order, and its tile table
+	const float4* qtab;
+	const int32_t* q_len;
+	int q_max;
+	const float4* tsorted;   // the target cloud
+	const float4* ttab;
+	const int32_t* t_len;
+	int t_max;
+	unsigned long long* key; // (n, q_max), at the queries' original indices
+};
+struct TileQueryArgs { TileQueryDir d[2]; unsigned* counter; };
+
+__global__ __launch_bounds__(256) void nn_tile_query_kernel(const TileQueryArgs a) {
+	__shared__ float4 tl[4][TILE_PTS / 8 * 6];   // a wave's target tile: per group of eight, x0..x7, y0..y7, z0..z7
+	__shared__ int ti[4][TILE_PTS];              // their original indices
+	const int dir = blockIdx.z, n = blockIdx.y;
+	if (a.counter && (blockIdx.x | blockIdx.y | blockIdx.z | threadIdx.x) == 0) *a.counter = 0u;
+	const int q_max = dir ? a.d[1].q_max : a.d[0].q_max, t_max = dir ? a.d[1].t_max : a.d[0].t_max;
+	const int32_t* q_len = dir ? a.d[1].q_len : a.d[0].q_len;
+	const int32_t* t_len = dir ? a.d[1].t_len : a.d[0].t_len;
+	const int p1 = min(max(q_len ? q_len[n] : q_max, 0), q_max), p2 = min(max(t_len ? t_len[n] : t_max, 0), t_max);
+	unsigned long long* kout = (dir ? a.d[1].key : a.d[0].key) + (int64_t)n * q_max;
+	// padding rows
+	for (int r = p1 + blockIdx.x * 256 + threadIdx.x; r < q_max; r += gridDim.x * 256) kout[r] = ~0ull;
+	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	const int qt = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + wave);
+	if (qt >= (p1 + TILE_PTS - 1) / TILE_PTS) return;
+	const float4* __restrict__ qsorted = (dir ? a.d[1].qsorted : a.d[0].qsorted) + (int64_t)n * q_max;
+	const float4* __restrict__ qtab = (dir ? a.d[1].qtab : a.d[0].qtab) + (int64_t)n * ((q_max + TILE_PTS - 1) / TILE_PTS) * 2;
+	const float4* __restrict__ tsorted = (dir ? a.d[1].tsorted : a.d[0].tsorted) + (int64_t)n * t_max;
+	const float4* __restrict__ ttab = (dir ? a.d[1].ttab : a.d[0].ttab) + (int64_t)n * ((t_max + TILE_PTS - 1) / TILE_PTS) * 2;
+	const float4 qb0 = qtab[2 * qt], qb1 = qtab[2 * qt + 1];
+	const int qstart = __builtin_amdgcn_readfirstlane(__float_as_int(qb0.w)), qcnt = __builtin_amdgcn_readfirstlane(__float_as_int(qb1.w));
+	if (qcnt <= 0) return;
+	// (lanes past the tile's last query repeat it: they change no wave maximum and store nothing)
+	const float4 q = qsorted[min(max(qstart, 0) + min(lane, qcnt - 1), p1 - 1)];
+	const int ntt = (p2 + TILE_PTS - 1) / TILE_PTS;
+	// ---- lower bounds to the target tiles lane and lane + 64
+	float lb[2];
+	int tstart[2], tcnt[2];
+#pragma unroll
+	for (int h = 0; h < 2; ++h) {
+		const int t = h * 64 + lane;
+		lb[h] = INFINITY; tstart[h] = 0; tcnt[h] = 0;
+		if (t < ntt) {
+			const float4 b0 = ttab[2 * t], b1 = ttab[2 * t + 1];
+			const float gx = fmaxf(0.f, fmaxf(b0.x - qb1.x, qb0.x - b1.x)), gy = fmaxf(0.f, fmaxf(b0.y - qb1.y, qb0.y - b1.y)),
+						gz = fmaxf(0.f, fmaxf(b0.z - qb1.z, qb0.z - b1.z));
+			lb[h] = __builtin_fmaf(gz, gz, __builtin_fmaf(gy, gy, gx * gx));
+			tstart[h] = __float_as_int(b0.w); tcnt[h] = __float_as_int(b1.w);
+		}
+	}
+	// ---- tiles in the order of their lower bounds: the nearest first, and the next one's points travel while a tile is scanned.  A tile
+	// leaves the order when it is picked (its bound becomes ~0); the search ends at the first pick above the wave's worst best distance --
+	// every tile still in the order is at least as far.
+	unsigned ord[2] = {lane < ntt ? __float_as_uint(lb[0]) : ~0u, 64 + lane < ntt ? __float_as_uint(lb[1]) : ~0u};
+	unsigned picked_lb = ~0u;
+	auto pick = [&]() -> int {
+		picked_lb = ~tile_wave_max(~min(ord[0], ord[1]));
+		if (picked_lb == ~0u) return -1;
+		const unsigned long long b0 = __ballot(ord[0] == picked_lb);
+		const int tt = b0 ? __builtin_ctzll(b0) : 64 + __builtin_ctzll(__ballot(ord[1] == picked_lb));
+		if (lane == (tt & 63)) { if (tt < 64) ord[0] = ~0u; else ord[1] = ~0u; }
+		return tt;
+	};
+	const v2f qx = {q.x, q.x}, qy = {q.y, q.y}, qz = {q.z, q.z};
+	float best = INFINITY;
+	int gj = 0;
+	unsigned long long tie = ~0ull;
+	float4* L = tl[wave];
+	int* LI = ti[wave];
+	float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+	int vs = 0, vc = 0;
+	auto fetch = [&](int tt, float4& o, int& os, int& oc) {   // tile tt: its first point and size from the lane that holds them, its points
+		const int s0 = __builtin_amdgcn_readlane(tstart[0], tt & 63), s1 = __builtin_amdgcn_readlane(tstart[1], tt & 63);
+		const int c0 = __builtin_amdgcn_readlane(tcnt[0], tt & 63), c1 = __builtin_amdgcn_readlane(tcnt[1], tt & 63);
+		os = tt < 64 ? s0 : s1;
+		oc = min(max(tt < 64 ? c0 : c1, 0), TILE_PTS);
+		os = min(max(os, 0), max(p2 - oc, 0));
+		// the last group is padded with targets at an infinite distance: never '<' the running best
+		o = lane < oc ? tsorted[os + lane] : make_float4(1e30f, 1e30f, 1e30f, __int_as_float(0x7fffffff));
+	};
+	int t = pick();
+	if (t >= 0) fetch(t, v, vs, vc);
+	while (t >= 0) {
+		// ---- stage the tile (this wave's own LDS: its LDS operations execute in order)
+		asm volatile("" ::: "memory");
+		{
+			float* Lf = reinterpret_cast<float*>(L);
+			const int g = lane >> 3, c = lane & 7;
+			Lf[g * 24 + c] = v.x; Lf[g * 24 + 8 + c] = v.y; Lf[g * 24 + 16 + c] = v.z;
+			LI[lane] = __float_as_int(v.w);
+		}
+		asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+		const int base = vs, ng = __builtin_amdgcn_readfirstlane((vc + 7) >> 3);
+		t = pick();
+		const unsigned t_lb = picked_lb;
+		if (t >= 0) fetch(t, v, vs, vc);
+		float4 A[6], B[6];
+#pragma unroll
+		for (int i = 0; i < 6; ++i) A[i] = L[i];
+#pragma unroll 2
+		for (int g = 0; g < ng; ++g) {
+			const int gn = min(g + 1, ng - 1);   // (the next group's reads are in flight during this group's arithmetic)
+#pragma unroll
+			for (int i = 0; i < 6; ++i) B[i] = L[6 * gn + i];
+#define FIND_TILE_D2(X, Y, Z, lo, hi) ({ const v2f dx = qx - v2f{X.lo, X.hi}, dy = qy - v2f{Y.lo, Y.hi}, dz = qz - v2f{Z.lo, Z.hi};   \
+										 __builtin_elementwise_fma(dz, dz, __builtin_elementwise_fma(dy, dy, dx * dx)); })
+			const v2f d0 = FIND_TILE_D2(A[0], A[2], A[4], x, y), d1 = FIND_TILE_D2(A[0], A[2], A[4], z, w);
+			const v2f d2 = FIND_TILE_D2(A[1], A[3], A[5], x, y), d3 = FIND_TILE_D2(A[1], A[3], A[5], z, w);
+#undef FIND_TILE_D2
+			const float m = fminf(fminf(fminf(d0.x, d0.y), fminf(d1.x, d1.y)), fminf(fminf(d2.x, d2.y), fminf(d3.x, d3.y)));
+			if (m == best) {   // a tie with the running best (duplicated points): its targets' keys
+				const float dd[8] = {d0.x, d0.y, d1.x, d1.y, d2.x, d2.y, d3.x, d3.y};
+#pragma unroll
+				for (int c = 0; c < 8; ++c)
+					if (dd[c] == best) tie = min(tie, nn_key(dd[c], LI[8 * g + c]));
+			}
+			if (m < best) { best = m; gj = base + 8 * g; }
+#pragma unroll
+			for (int i = 0; i < 6; ++i) A[i] = B[i];
+		}
+		// ---- the wave's worst best distance (non-negative floats order as their bit patterns); tiles above it are out for good
+		if (t >= 0 && t_lb > tile_wave_max(__float_as_uint(best))) t = -1;
+	}
+	// ---- the kept group -> keys of its targets (past the tile's end: other targets of the cloud, harmless), and the ties
+	unsigned long long key = tie;
+	if (ntt > 0) {
+#pragma unroll
+		for (int c = 0; c < 8; ++c) {
+			const int j = gj + c;
+			if (j < p2) {
+				const float4 s = tsorted[j];
+				key = min(key, nn_key(nn_dist(q.x, q.y, q.z, s.x, s.y, s.z), __float_as_int(s.w)));
+			}
+		}
+	}
+	const int qi = __float_as_int(q.w);
+	if (lane < qcnt && qi >= 0 && qi < p1) kout[qi] = key;
+}
+
 // queries per lane and target splits of a launch: enough blocks to give every SIMD work at batch 1, whole waves of blocks at batch 16
 static void nn_shape(int64_t blocks_np1, int64_t p2_max, int* np, int* splits) {
 	*np = blocks_np1 >= 4096 ? 2 : 1;
@@ -1074,6 +1469,7 @@ struct ChamferWs {
 	float4 *sorted_x, *sorted_y;
 	int32_t *cells_x, *cells_y;
 	float *box_x, *box_y;
+	float4 *tab_x, *tab_y;
 	int64_t bytes;
 };
 // Per cloud; below, all pairs.  Alone, the grid wins from ~2000 points on (16 x 5000 x 5000, forward + backward: 0.097 against 0.151 ms;
@@ -1082,6 +1478,24 @@ struct ChamferWs {
 // 134 us of packed arithmetic, the step 2.4 - 2.6 instead of 2.19 ms -- so the 5000-sample training clouds stay with all pairs and the
 // grid serves the evaluation sizes (eval_3d.py:148: 10 000 samples).  Bits of find_render_switches: 512 = never the grid, 1024 = the grid from 64 points on (tests).
 constexpr int64_t GRID_MIN_POINTS = 8192;
+// The balanced tiles (nn_tile_*_kernel) between the two.  Alone, forward only (HIP events, one box): 16 x 5000^2 90 us against 133 all
+// pairs and 180 through the grid; 32 x 5000^2 116 / 246; 16 x 8000^2 124 / 307; but 8 x 5000^2 85 / 89, 4 x 5000^2 80 / 56,
+// 1 x 5000^2 78 / 23, 16 x 2500^2 73 / 56, 16 x 1000^2 56 / 24: the build is one workgroup per cloud and takes ~50 us whatever the batch
+// (the search 30 us at batch 16, 21 at batch 1), so the tiles pay from about 3e8 pairs per call on and all pairs with target splits stay
+// faster below -- batch 1 and the small clouds keep nn_kernel.  In the training step (16 feet, beside the texture pass's MLP chain) the
+// build takes 65 us and the search 106 us, but they leave the chain alone: chamfer_reduce_kernel 121 -> 9 us, the split_w_kernel in front
+// of fused6_kernel<2> 58 -> 7 us, fused6_kernel<2> forward 146 -> 132 us average; the step 1.578 - 1.582 -> 1.479 - 1.487 ms, three
+// alternating runs each on one box (profiles/r07_headline_step_stats*.csv).
+// Bits of find_render_switches: 16384 = the tiles from 64 points per cloud on (up to TILE_MAX_POINTS, the build's limit), 32768 = never
+// the tiles; 512 (all pairs) forbids them too.
+constexpr int64_t TILE_MIN_POINTS = 2048, TILE_MIN_PAIRS = 300000000;
+static bool tile_path(int64_t n, int64_t p1_max, int64_t p2_max) {
+	if (g_raster_ablate & (512 | 32768)) return false;
+	if (std::max(p1_max, p2_max) > TILE_MAX_POINTS) return false;
+	if (g_raster_ablate & 16384) return std::min(p1_max, p2_max) >= 64;
+	if (g_raster_ablate & 1024) return false;
+	return n * p1_max * p2_max >= TILE_MIN_PAIRS && std::min(p1_max, p2_max) >= TILE_MIN_POINTS && std::max(p1_max, p2_max) < GRID_MIN_POINTS;
+}
 static void carve_chamfer(int64_t n, int64_t p1_max, int64_t p2_max, void* ws, ChamferWs* o) {
 	Carver c(ws);
 	o->kx = c.take<unsigned long long>(n * p1_max);
@@ -1096,6 +1510,9 @@ static void carve_chamfer(int64_t n, int64_t p1_max, int64_t p2_max, void* ws, C
 	o->cells_y = c.take<int32_t>(n * (NG3 + 1));
 	o->box_x = c.take<float>(n * 8);
 	o->box_y = c.take<float>(n * 8);
+	// the tile tables of the two clouds (nn_tile_*_kernel; the points in tile order share sorted_x / sorted_y with the grid: one path runs)
+	o->tab_x = c.take<float4>(n * cdiv(p1_max, TILE_PTS) * 2);
+	o->tab_y = c.take<float4>(n * cdiv(p2_max, TILE_PTS) * 2);
 	o->bytes = c.off;
 }
 
@@ -1114,6 +1531,24 @@ extern "C" int find_chamfer_fwd(const float* x, const int32_t* x_len, const floa
 	carve_chamfer(n, p1_max, p2_max, ws, &w);
 	if (ws_bytes < w.bytes) { set_error("find_chamfer_fwd: workspace too small"); return FIND_EWORKSPACE; }
 	hipStream_t s = (hipStream_t)stream;
+	if (tile_path(n, p1_max, p2_max)) {
+		// each cloud is cut once: x's tiles are the query groups of direction 0 (x -> y) and the targets of direction 1
+		TileBuildArgs b = {};
+		b.d[0] = TileDir{x, x_len, (int)p1_max, w.sorted_x, w.tab_x};
+		b.d[1] = TileDir{y, y_len, (int)p2_max, w.sorted_y, w.tab_y};
+		hipLaunchKernelGGL(nn_tile_build_kernel, dim3((unsigned)n, 2), dim3(1024), 0, s, b);
+		FIND_LAUNCH_CHECK("nn_tile_build_kernel");
+		TileQueryArgs q = {};
+		q.d[0] = TileQueryDir{w.sorted_x, w.tab_x, x_len, (int)p1_max, w.sorted_y, w.tab_y, y_len, (int)p2_max, w.kx};
+		q.d[1] = TileQueryDir{w.sorted_y, w.tab_y, y_len, (int)p2_max, w.sorted_x, w.tab_x, x_len, (int)p1_max, w.ky};
+		q.counter = w.counter;
+		hipLaunchKernelGGL(nn_tile_query_kernel, dim3((unsigned)cdiv(cdiv(std::max(p1_max, p2_max), TILE_PTS), 4), (unsigned)n, 2), dim3(256), 0, s, q);
+		FIND_LAUNCH_CHECK("nn_tile_query_kernel");
+		hipLaunchKernelGGL(chamfer_reduce_kernel, dim3((unsigned)n, 2), dim3(1024), 0, s, w.kx, x_len, (int)p1_max, w.ky, y_len, (int)p2_max, (int)n, w.partial, w.counter,
+						   loss);
+		FIND_LAUNCH_CHECK("chamfer_reduce_kernel");
+		return FIND_OK;
+	}
 	const int64_t grid_from = (g_raster_ablate & 1024) ? 64 : GRID_MIN_POINTS;
 	if (p1_max >= grid_from && p2_max >= grid_from && !(g_raster_ablate & 512)) {
 		// targets of direction 0 (x -> y) are y's points, of direction 1 x's
