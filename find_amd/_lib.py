@@ -116,6 +116,8 @@ PROTOTYPES = {
 	'find_chamfer_ws_bytes': (c_int64, [_I, _I, _I]),
 	'find_chamfer_fwd': (c_int, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _I, _P]),
 	'find_chamfer_bwd': (c_int, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _I, _P, _P, _P]),
+	'find_chamfer_surface_bwd_ws_bytes': (c_int64, [_I, _I, _I]),
+	'find_chamfer_surface_bwd': (c_int, [_P, _P, _P, _I, _I, _I, _P, _P, _I, _P, _I, _P, _P, _I, _I, _P, _P, _I, _P]),
 	'find_masked_mse_fwd': (c_int, [_P, _P, _I, _P, _P]),
 	'find_masked_mse_bwd': (c_int, [_P, _P, _I, _P, _P, _P]),
 	'find_image_mse_ws_bytes': (c_int64, []),

@@ -598,6 +598,216 @@ __global__ void chamfer_bwd_kernel(const float* __restrict__ x, const int32_t* _
 	}
 }
 
+// The same gradient taken straight to the vertices of the mesh x was sampled from (find_chamfer_surface_bwd): x_s = sum_c w_c v[faces[face_idx[s]][c]].
+// Workgroup (slice, foot) owns a range of the foot's samples and keeps two sums in LDS: d_x of its samples and an image of the foot's
+// (V, 3) gradient.  (1) d_x[s] = c0 (x_s - y_j) of direction 0, one plain store per sample; (2) it scans the keys of ALL the foot's
+// direction-1 items and adds -c1 (y_k - x_j) to d_x[j] where j is one of its samples; (3) w_c d_x[s] goes to the three corners' rows of
+// the image; (4) the image is stored with plain 16-byte stores.  The same association as chamfer_bwd_kernel + sample_bwd_kernel (d_x
+// first, then its weighted scatter), so the same rounding behaviour, without d_x in memory, zero fills or global float atomics (one lane
+// per destination row is the slowest shape of a global float atomic, 0.08 TB/s: 1.2 M of them made the pair 100 - 135 us in the step).
+// The LDS adds are compare-and-swaps on the words' bits: gfx950 executes ds_add_f32 a lane at a time, 81 ns per wave-instruction per CU
+// whatever the addresses, against 3.9 ns for ds_add_u32 and 4.2 ns for ds_write_b32 (measured); ds_cmpst_rtn_b32 runs at
+// the integer rate and a retry is needed only where two lanes meet on a word.
+// The image starts `head` floats into the LDS so that its 16-byte groups and those of the destination line up whatever the
+// destination's address (V * 12 is no multiple of 16 in general).  A thread issues each stage's loads for SCB_BATCH items at once.
+constexpr int SCB_THREADS = 1024, SCB_BATCH = 5;
+constexpr int64_t SCB_LDS_MAX = 160 * 1024;   // one workgroup may take the whole LDS of a CU
+struct SurfBwdArgs {
+	const float *x, *y;
+	const int32_t* y_len;
+	const unsigned long long *kx, *ky;
+	const float* g_loss;
+	const int32_t* faces;
+	int64_t faces_mesh_stride;
+	const int32_t* face_idx;
+	const float* uv;
+	int p1, p2_max, n_clouds, n_verts, n_faces;
+	int range;                                    // samples per slice
+	float* out;                                   // d_verts, or the slices' slabs
+	int64_t out_foot_stride, out_slice_stride;    // in floats
+};
+
+// word[k] += add[k] for the open k, all N swaps in flight together; cur[k]: a guess of what word[k] holds (any value: a wrong one costs a round)
+template <int N>
+__device__ __forceinline__ void lds_add_cas(unsigned* const (&word)[N], const float (&add)[N], unsigned (&cur)[N], bool (&open)[N]) {
+	bool any = true;
+	while (any) {
+		unsigned got[N];
+#pragma unroll
+		for (int k = 0; k < N; ++k)
+			if (open[k]) got[k] = atomicCAS(word[k], cur[k], __float_as_uint(__uint_as_float(cur[k]) + add[k]));
+		any = false;
+#pragma unroll
+		for (int k = 0; k < N; ++k)
+			if (open[k]) {
+				open[k] = got[k] != cur[k];
+				cur[k] = got[k];
+				any = any || open[k];
+			}
+	}
+}
+
+__global__ __launch_bounds__(SCB_THREADS) void chamfer_surface_bwd_kernel(const SurfBwdArgs a) {
+	extern __shared__ __attribute__((aligned(16))) float scb_lds[];
+	const int tid = threadIdx.x, n = blockIdx.y, slice = blockIdx.x;
+	const int V3 = a.n_verts * 3;
+	float* dst = a.out + (int64_t)n * a.out_foot_stride + (int64_t)slice * a.out_slice_stride;
+	const int head = (int)((reinterpret_cast<uintptr_t>(dst) >> 2) & 3);
+	float* img = scb_lds + head;
+	const int n_quads = (head + V3 + 3) >> 2;
+	float* dxs = scb_lds + ((V3 + 3 + 3) & ~3);   // behind the image whatever `head`
+	for (int q = tid; q < n_quads; q += SCB_THREADS) reinterpret_cast<float4*>(scb_lds)[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+
+	const int p1 = a.p1, p2_max = a.p2_max;
+	const int p2_len = a.y_len ? a.y_len[n] : p2_max;
+	const int p2 = min(max(p2_len, 0), p2_max);
+	const float gl = *a.g_loss;
+	const float c0 = 2.0f * gl / ((float)a.n_clouds * (float)max(p1, 1));
+	const float c1 = 2.0f * gl / ((float)a.n_clouds * (float)max(p2_len, 1));
+	const int r0 = min((int)((int64_t)slice * a.range), p1), r1 = min(r0 + a.range, p1);   // this slice's samples
+	const float* xn = a.x + (int64_t)n * p1 * 3;
+	const float* yn = a.y + (int64_t)n * p2_max * 3;
+	const unsigned long long* kxn = a.kx + (int64_t)n * p1;
+	const unsigned long long* kyn = a.ky + (int64_t)n * p2_max;
+	const int32_t* fin = a.face_idx + (int64_t)n * p1;
+	const float* uvn = a.uv + (int64_t)n * p1 * 2;
+	const int32_t* fn = a.faces + (int64_t)n * a.faces_mesh_stride;
+	// every load below goes to an address inside its array (row 0 stands in for an item that contributes nothing)
+
+	// (1) direction 0: d_x[s] = c0 (x_s - y_j), 0 for a sample without a neighbour (key ~0: an empty target cloud)
+	for (int s0 = r0; s0 < r1; s0 += SCB_THREADS * SCB_BATCH) {
+		unsigned long long key[SCB_BATCH];
+		int s[SCB_BATCH];
+#pragma unroll
+		for (int b = 0; b < SCB_BATCH; ++b) {
+			s[b] = s0 + b * SCB_THREADS + tid;
+			key[b] = kxn[min(s[b], r1 - 1)];
+		}
+		float3 pa[SCB_BATCH], pb[SCB_BATCH];
+		bool ok[SCB_BATCH];
+#pragma unroll
+		for (int b = 0; b < SCB_BATCH; ++b) {
+			const unsigned j = (unsigned)key[b];
+			ok[b] = key[b] != ~0ull && j < (unsigned)p2_max;
+			pa[b] = ld3(xn + (int64_t)min(s[b], r1 - 1) * 3);
+			pb[b] = ld3(yn + (int64_t)(ok[b] ? j : 0u) * 3);
+		}
+#pragma unroll
+		for (int b = 0; b < SCB_BATCH; ++b) {
+			if (s[b] >= r1) continue;
+			float* o = dxs + (s[b] - r0) * 3;
+			o[0] = ok[b] ? c0 * (pa[b].x - pb[b].x) : 0.f;
+			o[1] = ok[b] ? c0 * (pa[b].y - pb[b].y) : 0.f;
+			o[2] = ok[b] ? c0 * (pa[b].z - pb[b].z) : 0.f;
+		}
+	}
+	__syncthreads();
+
+	// (2) direction 1: every y_k of the foot whose neighbour x_j is one of this slice's samples: d_x[j] -= c1 (y_k - x_j)
+	for (int k0 = 0; k0 < p2; k0 += SCB_THREADS * SCB_BATCH) {
+		unsigned long long key[SCB_BATCH];
+		int k[SCB_BATCH];
+#pragma unroll
+		for (int b = 0; b < SCB_BATCH; ++b) {
+			k[b] = k0 + b * SCB_THREADS + tid;
+			key[b] = kyn[min(k[b], p2 - 1)];
+		}
+		float3 pa[SCB_BATCH], pb[SCB_BATCH];
+		bool ok[SCB_BATCH];
+		int j[SCB_BATCH];
+#pragma unroll
+		for (int b = 0; b < SCB_BATCH; ++b) {
+			j[b] = (int)(unsigned)key[b];
+			ok[b] = k[b] < p2 && key[b] != ~0ull && j[b] >= r0 && j[b] < r1;
+			j[b] = ok[b] ? j[b] : r0;
+			pa[b] = ld3(yn + (int64_t)min(k[b], p2 - 1) * 3);
+			pb[b] = ld3(xn + (int64_t)min(j[b], p1 - 1) * 3);
+		}
+#pragma unroll
+		for (int b = 0; b < SCB_BATCH; ++b) {
+			if (!ok[b]) continue;
+			unsigned* row = reinterpret_cast<unsigned*>(dxs) + (j[b] - r0) * 3;
+			unsigned* const word[3] = {row, row + 1, row + 2};
+			const float add[3] = {-c1 * (pa[b].x - pb[b].x), -c1 * (pa[b].y - pb[b].y), -c1 * (pa[b].z - pb[b].z)};
+			typedef volatile __attribute__((address_space(3))) unsigned lds_word;   // (a volatile read of a generic pointer is a flat load)
+			unsigned cur[3] = {*(lds_word*)row, *(lds_word*)(row + 1), *(lds_word*)(row + 2)};
+			bool open[3] = {true, true, true};
+			lds_add_cas<3>(word, add, cur, open);
+		}
+	}
+	__syncthreads();
+
+	// (3) the sampler's backward: w_c d_x[s] to the rows of the face's three corners
+	for (int s0 = r0; s0 < r1; s0 += SCB_THREADS * SCB_BATCH) {
+		int s[SCB_BATCH], face[SCB_BATCH];
+		float u[SCB_BATCH][2];
+#pragma unroll
+		for (int b = 0; b < SCB_BATCH; ++b) {
+			s[b] = s0 + b * SCB_THREADS + tid;
+			const int ss = min(s[b], r1 - 1);
+			face[b] = fin[ss];
+			u[b][0] = uvn[(int64_t)ss * 2 + 0];
+			u[b][1] = uvn[(int64_t)ss * 2 + 1];
+		}
+		int vi[SCB_BATCH][3];
+		bool ok[SCB_BATCH];
+#pragma unroll
+		for (int b = 0; b < SCB_BATCH; ++b) {
+			ok[b] = s[b] < r1 && (unsigned)face[b] < (unsigned)a.n_faces;
+			const int32_t* fp = fn + (int64_t)(ok[b] ? face[b] : 0) * 3;
+			vi[b][0] = fp[0]; vi[b][1] = fp[1]; vi[b][2] = fp[2];
+		}
+#pragma unroll
+		for (int b = 0; b < SCB_BATCH; ++b) {
+			if (!ok[b]) continue;
+			const float* d = dxs + (s[b] - r0) * 3;
+			const float gx = d[0], gy = d[1], gz = d[2];
+			float w[3];
+			bary_weights(u[b], w);
+			unsigned* word[9];
+			float add[9];
+			unsigned cur[9];
+			bool open[9];
+#pragma unroll
+			for (int c = 0; c < 3; ++c) {
+				const bool in = (unsigned)vi[b][c] < (unsigned)a.n_verts;
+				unsigned* row = reinterpret_cast<unsigned*>(img) + 3 * (in ? vi[b][c] : 0);
+				word[3 * c + 0] = row + 0; word[3 * c + 1] = row + 1; word[3 * c + 2] = row + 2;
+				add[3 * c + 0] = w[c] * gx; add[3 * c + 1] = w[c] * gy; add[3 * c + 2] = w[c] * gz;
+				open[3 * c + 0] = open[3 * c + 1] = open[3 * c + 2] = in;
+				cur[3 * c + 0] = cur[3 * c + 1] = cur[3 * c + 2] = 0u;   // (+0: what an untouched word holds)
+			}
+			lds_add_cas<9>(word, add, cur, open);
+		}
+	}
+	__syncthreads();
+
+	// (4)
+	for (int q = tid; q < n_quads; q += SCB_THREADS) {
+		const float4 v = reinterpret_cast<const float4*>(scb_lds)[q];
+		const int e = 4 * q - head;   // dst + e is 16-byte aligned
+		if (e >= 0 && e + 3 < V3) {
+			*reinterpret_cast<float4*>(dst + e) = v;
+		} else {
+			const float r[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+			for (int k = 0; k < 4; ++k)
+				if (e + k >= 0 && e + k < V3) dst[e + k] = r[k];
+		}
+	}
+}
+
+// More than one slice per foot: their images, one slab each, summed in slice order.
+__global__ __launch_bounds__(256) void chamfer_surface_sum_kernel(const float* __restrict__ slabs, int n_slices, int64_t slab_stride, int V3,
+																  float* __restrict__ d_verts) {
+	const int n = blockIdx.y, e = blockIdx.x * 256 + threadIdx.x;
+	if (e >= V3) return;
+	const float* p = slabs + (int64_t)n * n_slices * slab_stride + e;
+	float s = 0.f;
+	for (int k = 0; k < n_slices; ++k) s += p[(int64_t)k * slab_stride];
+	d_verts[(int64_t)n * V3 + e] = s;
+}
+
 __global__ void nn_bwd_kernel(const float* __restrict__ x, const int32_t* __restrict__ x_len, const float* __restrict__ y,
 							  const int32_t* __restrict__ idx, const float* __restrict__ w, int p1_max, int p2_max,
 							  float* __restrict__ d_x, float* __restrict__ d_y) {
@@ -1599,6 +1809,67 @@ extern "C" int find_chamfer_bwd(const float* x, const int32_t* x_len, const floa
 	hipLaunchKernelGGL(chamfer_bwd_kernel, dim3((unsigned)cdiv(std::max(p1_max, p2_max), 256), (unsigned)n, 2), dim3(256), 0, (hipStream_t)stream, x, x_len,
 					   (int)p1_max, y, y_len, (int)p2_max, w.kx, w.ky, g_loss, (int)n, d_x, d_y);
 	FIND_LAUNCH_CHECK("chamfer_bwd_kernel");
+	return FIND_OK;
+}
+
+// Slices per foot of chamfer_surface_bwd_kernel (each takes an equal range of the foot's samples).  Alone, 5000 samples on 6890 vertices,
+// us per call with 1 / 2 / 4 / 8 / 16 / 32 slices: 1 foot 38 / 26 / 20 / 17 / 18 / 20, 8 feet 39 / 27 / 21 / 19 / 22 / 29, 16 feet
+// 40 / 28 / 22 / 23 / 26 / 37, 32 feet 42 / 31 / 27 / 26 / 41 / 66.  In the 16-foot step 8 and 16 slices come out
+// 3 - 6 us ahead of 4, and 1 slice (16 workgroups for 40 us) loses 20 - 30 us to them.  Past 32 feet nothing is measured: the workgroups
+// are kept near 256.  A cloud of at most one round of threads is not cut.  Bits 0x70000 of find_render_switches force 1 << (field - 1) slices.
+static int surf_bwd_slices(int64_t n, int64_t n_samples) {
+	const int forced = (g_raster_ablate >> 16) & 7;
+	if (forced) return 1 << (forced - 1);
+	if (n_samples <= SCB_THREADS) return 1;
+	return n <= 16 ? 8 : n <= 32 ? 4 : n <= 128 ? 2 : 1;
+}
+// the image (with room for its alignment shift) and d_x of a slice's samples
+static int64_t surf_bwd_lds(int64_t n_verts, int64_t range) { return align_up((((n_verts * 3 + 6) & ~(int64_t)3) + range * 3) * (int64_t)sizeof(float), 16); }
+
+extern "C" int64_t find_chamfer_surface_bwd_ws_bytes(int64_t n, int64_t n_verts, int64_t n_samples) {
+	if (bad_dims(n, n_samples) || n_verts < 1) return -1;
+	const int slices = surf_bwd_slices(n, n_samples);
+	if (surf_bwd_lds(n_verts, cdiv(n_samples, slices)) > SCB_LDS_MAX) return -1;
+	return slices == 1 ? 0 : n * slices * align_up(n_verts * 3, 64) * (int64_t)sizeof(float);
+}
+
+extern "C" int find_chamfer_surface_bwd(const float* x, const float* y, const int32_t* y_len, int64_t n, int64_t p1, int64_t p2_max, const float* g_loss,
+										const void* chamfer_ws, int64_t chamfer_ws_bytes, const int32_t* faces, int64_t faces_batch, const int32_t* face_idx,
+										const float* uv, int64_t n_verts, int64_t n_faces, float* d_verts, void* ws, int64_t ws_bytes, void* stream) {
+	FIND_REQUIRE(x && y && g_loss && chamfer_ws && faces && face_idx && uv && d_verts, "find_chamfer_surface_bwd: NULL argument");
+	FIND_REQUIRE(!bad_dims(n, p1) && !bad_dims(n, p2_max) && n_verts >= 1 && !bad_dims(n, n_faces), "find_chamfer_surface_bwd: bad sizes");
+	FIND_REQUIRE(faces_batch == 1 || faces_batch == n, "find_chamfer_surface_bwd: faces_batch must be 1 or n");
+	const int64_t need = find_chamfer_surface_bwd_ws_bytes(n, n_verts, p1);
+	FIND_REQUIRE(need >= 0, "find_chamfer_surface_bwd: %lld vertices do not fit one workgroup's LDS (find_chamfer_surface_bwd_ws_bytes < 0)", (long long)n_verts);
+	ChamferWs w;
+	carve_chamfer(n, p1, p2_max, const_cast<void*>(chamfer_ws), &w);
+	if (chamfer_ws_bytes < w.bytes) { set_error("find_chamfer_surface_bwd: Chamfer workspace too small"); return FIND_EWORKSPACE; }
+	if (ws_bytes < need || (need > 0 && !ws)) { set_error("find_chamfer_surface_bwd: workspace too small"); return FIND_EWORKSPACE; }
+	const int slices = surf_bwd_slices(n, p1);
+	const int64_t slab = align_up(n_verts * 3, 64);
+	const int lds = (int)surf_bwd_lds(n_verts, cdiv(p1, slices));
+	static bool lds_granted[64] = {};   // per device: the kernel may ask for more than the default 64 KiB
+	int dev = 0;
+	if (lds > 64 * 1024 && (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64 || !lds_granted[dev])) {
+		hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&chamfer_surface_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SCB_LDS_MAX);
+		if (e != hipSuccess) { set_error("find_chamfer_surface_bwd: hipFuncSetAttribute(MaxDynamicSharedMemorySize): %s", hipGetErrorString(e)); return FIND_ELAUNCH; }
+		if (dev >= 0 && dev < 64) lds_granted[dev] = true;
+	}
+	hipStream_t s = (hipStream_t)stream;
+	SurfBwdArgs a = {};
+	a.x = x; a.y = y; a.y_len = y_len; a.kx = w.kx; a.ky = w.ky; a.g_loss = g_loss;
+	a.faces = faces; a.faces_mesh_stride = faces_batch == 1 ? 0 : n_faces * 3; a.face_idx = face_idx; a.uv = uv;
+	a.p1 = (int)p1; a.p2_max = (int)p2_max; a.n_clouds = (int)n; a.n_verts = (int)n_verts; a.n_faces = (int)n_faces;
+	a.range = (int)cdiv(p1, slices);
+	if (slices == 1) { a.out = d_verts; a.out_foot_stride = n_verts * 3; a.out_slice_stride = 0; }
+	else { a.out = (float*)ws; a.out_foot_stride = slices * slab; a.out_slice_stride = slab; }
+	hipLaunchKernelGGL(chamfer_surface_bwd_kernel, dim3((unsigned)slices, (unsigned)n), dim3(SCB_THREADS), (size_t)lds, s, a);
+	FIND_LAUNCH_CHECK("chamfer_surface_bwd_kernel");
+	if (slices > 1) {
+		hipLaunchKernelGGL(chamfer_surface_sum_kernel, dim3((unsigned)cdiv(n_verts * 3, 256), (unsigned)n), dim3(256), 0, s, (const float*)ws, slices, slab, (int)(n_verts * 3),
+						   d_verts);
+		FIND_LAUNCH_CHECK("chamfer_surface_sum_kernel");
+	}
 	return FIND_OK;
 }
 

@@ -756,7 +756,10 @@ class _SamplePoints(torch.autograd.Function):
 def sample_points(verts, faces, face_idx, uv, attr=None):
 	"""Gather half of sample_points_from_meshes with the draws (face_idx (N,S), uv (N,S,2)) given.
 	Returns points (N,S,3) [and attr sampled with the same barycentric weights]."""
-	return _SamplePoints.apply(verts, faces, face_idx, uv, attr)
+	r = _SamplePoints.apply(verts, faces, face_idx, uv, attr)
+	if attr is None and torch.is_grad_enabled() and verts.requires_grad:
+		_remember_surface(r, verts, _faces_i32(faces), face_idx.to(torch.int32).contiguous(), _c(uv))
+	return r
 
 
 class _NoCtx:
@@ -864,6 +867,8 @@ def sample_surface(verts, faces, rnd, attr=None):
 	Returns (points (N,S,3), attr samples or None, face_idx (N,S) int32, uv (N,S,2))."""
 	if torch.is_grad_enabled() and (verts.requires_grad or (attr is not None and attr.requires_grad)):
 		r = _SampleSurface.apply(verts, faces, rnd, attr)
+		if attr is None and verts.requires_grad:
+			_remember_surface(r[0], verts, _faces_i32(faces), r[1], r[2])
 	else:
 		# nothing to differentiate (a GT scan, an evaluation): the same code without the autograd Function around it (its bookkeeping is
 		# 20 us of host time per call, twice per training step, on a step whose host time is what a slow host makes the step time)
@@ -1015,6 +1020,95 @@ def chamfer_distance(x, y, x_lengths=None, y_lengths=None):
 	"""pytorch3d.loss.chamfer_distance with its defaults (bidirectional, squared L2, point mean, batch mean).
 	Returns (loss, None) like PyTorch3D (the second value is the normals term, never used by FIND: losses.py:77,85,88)."""
 	return _Chamfer.apply(x, y, x_lengths, y_lengths), None
+
+
+class _SurfaceChamfer(torch.autograd.Function):
+	"""chamfer_distance(x, y) for x = the samples a sampler call drew on the mesh `verts`, with the two backward passes as one: the forward
+	is find_chamfer_fwd on x as _Chamfer's, the backward ONE kernel from the Chamfer neighbours to d_verts (find_chamfer_surface_bwd): no
+	d_x, no zero fills, no global float atomics.  The gradient reaches verts only (x's own node is left out of the graph, y is a constant)."""
+
+	@staticmethod
+	def forward(ctx, verts, x, faces, face_idx, uv, y, y_len):
+		_require_gpu(x, y)
+		L = _lib.lib()
+		x, y = _c(x), _c(y)
+		N, S, _ = x.shape
+		if y.dim() != 3 or y.shape[0] != N or y.shape[2] != 3:
+			raise RuntimeError(f'find_amd.surface_chamfer: y must be ({N}, P2, 3), got {tuple(y.shape)}')
+		P2 = y.shape[1]
+		dev = x.device
+		yl = None if y_len is None else y_len.to(device=dev, dtype=torch.int32).contiguous()
+		ws = _ws(L.find_chamfer_ws_bytes(N, S, P2), dev)
+		loss = torch.empty((), device=dev, dtype=torch.float32)
+		check(L.find_chamfer_fwd(ptr(x), None, ptr(y), ptr(yl), N, S, P2, ptr(loss), ptr(ws), ws.numel(), current_stream(dev)), 'find_chamfer_fwd')
+		ctx.save_for_backward(x, y, ws, faces, face_idx, uv)
+		ctx.y_len = yl
+		ctx.dims = (N, verts.shape[1], faces.shape[-2], S, P2, 1 if faces.dim() == 2 else faces.shape[0])
+		return loss
+
+	@staticmethod
+	def backward(ctx, g):
+		if not ctx.needs_input_grad[0]:
+			return (None,) * 7
+		L = _lib.lib()
+		x, y, ws, faces, face_idx, uv = ctx.saved_tensors
+		N, V, F, S, P2, fb = ctx.dims
+		dev = x.device
+		d_verts = torch.empty(N, V, 3, device=dev, dtype=torch.float32)
+		bws = _ws(L.find_chamfer_surface_bwd_ws_bytes(N, V, S), dev)
+		check(L.find_chamfer_surface_bwd(ptr(x), ptr(y), ptr(ctx.y_len), N, S, P2, ptr(_c(g)), ptr(ws), ws.numel(), ptr(faces), fb, ptr(face_idx), ptr(uv), V, F,
+										 ptr(d_verts), ptr(bws), bws.numel(), current_stream(dev)), 'find_chamfer_surface_bwd')
+		return d_verts, None, None, None, None, None, None
+
+
+def _remember_surface(samples, verts, faces, face_idx, uv):
+	"""Note on a sampler's output what it was drawn from: surface_chamfer_distance needs the mesh and the draws, not the sampler's node."""
+	samples._find_surface = (verts, faces, face_idx, uv)
+
+
+def surface_of(samples):
+	"""(verts, faces, face_idx, uv) of samples that sample_surface / sample_points returned as they are (no attributes, a mesh that takes
+	a gradient), else None."""
+	return getattr(samples, '_find_surface', None)
+
+
+def surface_chamfer_fits(n_meshes, n_verts, n_samples):
+	"""Whether surface_chamfer takes these sizes: one mesh's (n_verts, 3) gradient and the gradient of a slice's samples have to fit one
+	workgroup's LDS."""
+	return _lib.lib().find_chamfer_surface_bwd_ws_bytes(n_meshes, n_verts, n_samples) >= 0
+
+
+def surface_chamfer_pays(n_meshes, n_samples):
+	"""The measured size rule: alone, at 5000 samples on 6890 vertices, the fused backward takes 17 - 27 us whatever the batch, the two
+	backward passes with their zero fills 13 / 15 / 21 / 34 / 60 / 109 us at 1 / 2 / 4 / 8 / 16 / 32 meshes: fused from
+	about 16 k samples per call on."""
+	return n_meshes * n_samples >= 16384
+
+
+def surface_chamfer_distance(samples, y, y_len=None):
+	"""chamfer_distance(samples, y, None, y_len)[0] for samples straight from a sampler (surface_of(samples) is not None), with the
+	sampler's and the Chamfer distance's backward passes fused into one kernel.  The same loss bit for bit; the gradient goes to the
+	sampled mesh's vertices, y counts as a constant."""
+	src = surface_of(samples)
+	if src is None:
+		raise RuntimeError('find_amd.surface_chamfer_distance: the samples are not the direct output of sample_surface / sample_points on a mesh that takes a gradient')
+	verts, faces, face_idx, uv = src
+	if not surface_chamfer_fits(verts.shape[0], verts.shape[1], samples.shape[1]):
+		raise RuntimeError(f'find_amd.surface_chamfer: {verts.shape[1]} vertices do not fit the fused backward (surface_chamfer_fits); '
+						   'use chamfer_distance')
+	return _SurfaceChamfer.apply(verts, samples.detach(), faces, face_idx, uv, y, y_len)
+
+
+def surface_chamfer(verts, faces, rnd, y, y_len=None):
+	"""chamfer_distance(sample_surface(verts, faces, rnd), y, None, y_len) with the two backward passes fused into one kernel: returns
+	(loss, samples (N,S,3)).  The forward is the same two calls; the loss's gradient reaches verts through the fused kernel only."""
+	if not surface_chamfer_fits(verts.shape[0], verts.shape[1], rnd.shape[1]):
+		raise RuntimeError(f'find_amd.surface_chamfer: {verts.shape[1]} vertices do not fit the fused backward (surface_chamfer_fits); '
+						   'use sample_surface + chamfer_distance')
+	samples = sample_surface(verts, faces, rnd)[0]
+	if surface_of(samples) is None:
+		raise RuntimeError('find_amd.surface_chamfer: verts must require a gradient (otherwise use sample_surface + chamfer_distance)')
+	return surface_chamfer_distance(samples, y, y_len), samples
 
 
 class _MaskedMSE(torch.autograd.Function):

@@ -6,6 +6,7 @@ MeshSmoothnessLoss, SilhouetteLoss, ContrastiveLoss, and the cluster mode of Res
 logits (the encoder is the caller's).  The other perceptual / Restyle modes need absent network weights or submodules and are out of
 scope."""
 import itertools
+import os
 
 import numpy as np
 import torch
@@ -15,6 +16,10 @@ from . import functional_render as FR
 from .structures import Meshes, TexturesUV, TexturesVertex
 
 nn = torch.nn
+# the Chamfer term's backward as one kernel from the neighbours to the predicted vertices (DisplacementLoss.forward) where the measured size
+# rule says it pays (functional.surface_chamfer_pays); FIND_FUSED_CHAMFER_BWD=0: never -- the sampler's and the Chamfer distance's own
+# backward passes, as before; 2: wherever it fits (tests, A/B runs)
+FUSED_CHAMFER_BWD = int(os.environ.get('FIND_FUSED_CHAMFER_BWD', '1'))
 
 
 def sample_points_from_meshes(meshes: Meshes, num_samples: int = 10000, return_textures: bool = False, generator=None, draws=None):
@@ -97,6 +102,13 @@ class DisplacementLoss(nn.Module):
 		if gt_samples is None:
 			gt_samples = sample_points_from_meshes(batch['mesh'], num_samples=num_samples)
 		pred_samples = sample_points_from_meshes(res['meshes'], num_samples=num_samples)
+		src = FN.surface_of(pred_samples) if FUSED_CHAMFER_BWD and z_cutoff is None and torch.is_grad_enabled() and not gt_samples.requires_grad else None
+		if (src is not None and (FUSED_CHAMFER_BWD >= 2 or FN.surface_chamfer_pays(pred_samples.shape[0], pred_samples.shape[1]))
+				and FN.surface_chamfer_fits(pred_samples.shape[0], src[0].shape[1], pred_samples.shape[1])):
+			# the predicted samples reach the Chamfer term as the sampler made them: the same loss, and a backward that goes from the neighbours
+			# straight to the predicted vertices in one kernel (functional.surface_chamfer_distance); the sampler's own node stays unused
+			g, gl = _compact_by_mask(gt_samples, gt_samples[..., 2] <= gt_z_cutoff) if gt_z_cutoff is not None else (gt_samples, None)
+			return dict(loss=FN.surface_chamfer_distance(pred_samples, g, gl))
 		if z_cutoff is not None:
 			p, pl = _compact_by_mask(pred_samples, pred_samples[..., 2] <= z_cutoff)
 			g, gl = _compact_by_mask(gt_samples, gt_samples[..., 2] <= z_cutoff)

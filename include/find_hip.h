@@ -222,8 +222,9 @@ int find_linear_wgrad(find_ctx* ctx, const float* dz, const float* x, int64_t n_
  * uniform grid from 64 points per cloud on, 16384 the balanced tiles from 64 points per cloud on (up to 8192), 32768 never the tiles
  * (geom.hip; tests/test_gpu_chamfer_tiles.py); 2048 / 4096 the band / the candidate-list rasteriser at every image size (default: the
  * band kernel from 384^2 pixels on, csrc/render_band.h -- the two agree in everything but the last bits of the alpha products); 8192
- * find_point_face_fwd never splits a mesh's faces over several workgroups (surface.hip; tests/test_gpu_surface.py).  Any other bit is
- * refused (FIND_EINVAL). */
+ * find_point_face_fwd never splits a mesh's faces over several workgroups (surface.hip; tests/test_gpu_surface.py); the field 0x70000, when
+ * k = (bits >> 16) & 7 is not 0: find_chamfer_surface_bwd cuts every foot into 1 << (k - 1) slices, whatever its size rule says
+ * (tests/test_gpu_surface_chamfer_bwd.py).  Any other bit is refused (FIND_EINVAL). */
 int find_render_switches(int64_t bits);
 /* ------------------------------------------------------------------------------------------------
  * Latent-table lookup.  Replaces LatentVector.__getitem__ with a tensor of indices (src/model/model.py:131-152;
@@ -432,6 +433,18 @@ int find_chamfer_fwd(const float* x, const int32_t* x_len, const float* y, const
 					 int64_t p2_max, float* loss, void* ws, int64_t ws_bytes, void* stream);
 int find_chamfer_bwd(const float* x, const int32_t* x_len, const float* y, const int32_t* y_len, int64_t n, int64_t p1_max,
 					 int64_t p2_max, const float* g_loss, const void* ws, int64_t ws_bytes, float* d_x, float* d_y, void* stream);
+/* find_chamfer_bwd and find_sample_points_bwd in one, for x = the samples find_sample_surface_fwd drew on a mesh (x (n,p1,3), all valid;
+ * face_idx, uv: what that call returned) and a y that takes no gradient: d_verts (n,n_verts,3) is OVERWRITTEN with the loss's gradient
+ * with respect to the mesh's vertices -- no zero-initialisation, no d_x in memory, no global float atomic: a workgroup sums d_x of a
+ * range of one foot's samples and then an image of that foot's d_verts in LDS and stores the image; several workgroups per foot write a
+ * slab each into ws, summed in a fixed order.  chamfer_ws: find_chamfer_fwd's workspace, untouched.
+ * find_chamfer_surface_bwd_ws_bytes < 0: the image (n_verts * 12 bytes) and a range's d_x do not fit one workgroup's LDS, or bad
+ * sizes -- use the two calls above. */
+int64_t find_chamfer_surface_bwd_ws_bytes(int64_t n, int64_t n_verts, int64_t n_samples);
+int find_chamfer_surface_bwd(const float* x, const float* y, const int32_t* y_len, int64_t n, int64_t p1, int64_t p2_max,
+							 const float* g_loss, const void* chamfer_ws, int64_t chamfer_ws_bytes, const int32_t* faces,
+							 int64_t faces_batch, const int32_t* face_idx, const float* uv, int64_t n_verts, int64_t n_faces,
+							 float* d_verts, void* ws, int64_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Masked colour error of TextureLossGTSpace (src/model/losses.py:43-57): mask = any(target < 1) per point, loss = mean over all
