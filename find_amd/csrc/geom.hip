@@ -82,6 +82,7 @@ __global__ void sample_bwd_kernel(const int32_t* __restrict__ faces, int64_t fac
 #pragma unroll
 	for (int c = 0; c < 3; ++c) {
 		const int vi = fp[c];
+		if (vi < 0) continue;   // a -1 row: sample_surface_kernel falls back to face 0 on a mesh without area, and face 0 of a mesh of padding only is one
 		atomicAdd(dv + 3 * vi + 0, w[c] * gx);
 		atomicAdd(dv + 3 * vi + 1, w[c] * gy);
 		atomicAdd(dv + 3 * vi + 2, w[c] * gz);

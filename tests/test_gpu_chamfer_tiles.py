@@ -1,6 +1,6 @@
 """The Chamfer search through balanced tiles (nn_tile_build_kernel / nn_tile_query_kernel, find_amd/csrc/geom.hip) against all pairs
 (nn_kernel): the same 64-bit keys (distance bits << 32 | lowest index) and the same loss, bit for bit, on the smallest shapes at which
-the tiling or the culling can go wrong.  Bit 16384 of the profiling switch forces the tile path from 64 points per cloud on, bit 512
+the tiling or the culling can go wrong, and at the build's capacity (8192 points, 8 per thread, 128 tiles).  Bit 16384 of the profiling switch forces the tile path from 64 points per cloud on, bit 512
 forces all pairs."""
 import pytest
 import torch
@@ -87,6 +87,14 @@ def _cases():
 	c['far from the origin, flat'] = (_sphere(g, 1, 800, r=0.02) * flat + 300.0, _sphere(g, 1, 800, r=0.02) * flat + 300.0, None, None)
 	c['many feet'] = (_sphere(g, 16, 320), _sphere(g, 16, 320), None, None)
 	c['training shape'] = (_sphere(g, 2, 5000), _sphere(g, 2, 5000, noise=2e-3), None, None)
+	# the build at its capacity: 8 points per thread (kmax = (p + 1023) >> 10) and 128 tiles; the default route sends clouds of up to 8191
+	# points here.  8192 on both sides: every tile full, all 128 rows of the tile table in use.
+	c['capacity'] = (_sphere(g, 1, 8192), _sphere(g, 1, 8192, noise=2e-3), None, None)
+	# every kmax from 2 to 8, tile counts 17, 33, 49, 65, 97, 113 and 128, different on the two sides of a pair
+	per_thread = (1025, 2049, 3073, 4097, 6145, 7169, 8191)
+	c['points per thread'] = (_sphere(g, 7, 8192), _sphere(g, 7, 8192, noise=2e-3), i32(*per_thread), i32(*reversed(per_thread)))
+	c['lopsided'] = (_sphere(g, 1, 64), _sphere(g, 1, 8192), None, None)
+	c['lopsided, reversed'] = (_sphere(g, 1, 8192), _sphere(g, 1, 64), None, None)
 	return c
 
 

@@ -468,3 +468,82 @@ def test_chamfer_through_the_grid_equals_brute_force_bit_for_bit():
 		assert (gx0 - gx1).abs().max().item() <= 3e-5 * max(gx1.abs().max().item(), 1e-12), name
 		assert (gy0 - gy1).abs().max().item() <= 3e-5 * max(gy1.abs().max().item(), 1e-12), name
 		assert torch.isfinite(l0).all()
+
+
+# ------------------------------------------------------------------------------------------------ knn1 backward (nn_bwd_kernel)
+def knn1_bwd_reference(x, y, idx, w):
+	"""float64 autograd of sum_i w_i |x_i - y[idx_i]|^2 over the rows with idx_i >= 0 (idx: oracle.geom_ref.knn1's) -> d_x, d_y and their
+	bounds, derived, not measured:
+	  d_x, per component   4 * 2^-24 * 2 |w| (|x| + |y_j|): the difference, the product with 2 w and the addition into the zeroed row;
+	  d_y, per component   (n_row + 3) * 2^-24 * sum |addend|: n_row float-atomic additions in any order (every partial sum is within
+	                       sum |addend|) and three roundings in forming an addend -2 w (x - y_j)."""
+	ok = idx >= 0
+	j = idx.clamp(min=0)
+	x64, y64 = x.double().requires_grad_(True), y.double().requires_grad_(True)
+	yj = torch.gather(y64, 1, j[..., None].expand(-1, -1, 3))
+	(w.double() * ((x64 - yj) ** 2).sum(-1) * ok).sum().backward()
+	wa = (w.double().abs() * ok)[..., None]
+	b_x = 4 * 2.0 ** -24 * 2 * wa * (x.double().abs() + yj.detach().abs())
+	addend = 2 * wa * (x.double() - yj.detach()).abs()
+	sum_abs = torch.zeros_like(y64).scatter_add_(1, j[..., None].expand(-1, -1, 3), addend).detach()
+	n_row = torch.zeros(y.shape[:2], dtype=torch.float64).scatter_add_(1, j, ok.double())
+	b_y = (n_row[..., None] + 3) * 2.0 ** -24 * sum_abs
+	return x64.grad, y64.grad, b_x, b_y, n_row
+
+
+def _knn1_bwd(x, y, xl, yl, w, need_x=True, need_y=True):
+	from find_amd import functional as FN
+	xg, yg = x.clone().cuda().requires_grad_(need_x), y.clone().cuda().requires_grad_(need_y)
+	d, i = FN.knn1(xg, yg, None if xl is None else xl.cuda(), None if yl is None else yl.cuda())
+	(d * w.cuda()).sum().backward()
+	torch.cuda.synchronize()
+	return (None if xg.grad is None else xg.grad.cpu()), (None if yg.grad is None else yg.grad.cpu()), i.cpu()
+
+
+def _knn1_bwd_cases():
+	g = torch.Generator().manual_seed(11)
+	x = torch.randn(3, 300, 3, generator=g)   # (the clouds and lengths of test_nn_ragged_and_ties)
+	y = torch.randn(3, 200, 3, generator=g)
+	c = {}
+	c['ragged'] = (x, y, torch.tensor([300, 17, 1]), torch.tensor([5, 200, 64]))
+	c['no query, no target'] = (x, y, torch.tensor([300, 0, 17]), torch.tensor([0, 200, 64]))
+	c['one point'] = (torch.randn(1, 1, 3, generator=g), torch.randn(1, 1, 3, generator=g), None, None)
+	# 100 queries around ONE target that exists twice (rows 7 and 150): 100 atomics on one row, and the lower index takes them all
+	yd = torch.randn(1, 200, 3, generator=g)
+	yd[0, 150] = yd[0, 7]
+	xd = torch.randn(1, 300, 3, generator=g)
+	xd[0, :100] = yd[0, 7] + 1e-3 * torch.randn(100, 3, generator=g)
+	c['one shared target'] = (xd, yd, None, None)
+	return c
+
+
+KNN1_BWD_CASES = _knn1_bwd_cases()
+
+
+@pytest.mark.parametrize('name', list(KNN1_BWD_CASES))
+def test_knn1_backward_against_float64(name):
+	"""find_nn_bwd, reached only through knn1(...)[0].backward(): a random upstream gradient of both signs, d_x (one thread per row) and
+	d_y (float atomics) against float64 autograd through the oracle's neighbours, within the derived bounds of knn1_bwd_reference; rows at
+	or past x_len and the rows of a cloud without targets are exactly 0."""
+	x, y, xl, yl = KNN1_BWD_CASES[name]
+	w = torch.randn(x.shape[:2], generator=torch.Generator().manual_seed(5))
+	assert (w > 0).any() and (w < 0).any() or w.numel() == 1
+	_, idx = G.knn1(x, y, xl, yl)
+	rx, ry, b_x, b_y, n_row = knn1_bwd_reference(x, y, idx, w)
+	dx, dy, i = _knn1_bwd(x, y, xl, yl, w)
+	assert torch.equal(i.long(), idx)
+	for what, got, ref, bound in (('d_x', dx, rx, b_x), ('d_y', dy, ry, b_y)):
+		err = (got.double() - ref).abs()
+		print(f'{name}: {what} max err {err.max().item():.3e}, largest bound {bound.max().item():.3e}, scale {ref.abs().max().item():.3e}')
+		assert torch.isfinite(got).all() and (err <= bound).all(), (name, what, float((err - bound).max()))
+	dead = idx < 0   # at or past x_len, or no target
+	assert (dx[dead] == 0).all() and (dy[n_row == 0] == 0).all()
+	if xl is not None:
+		assert dead.any()
+	if name == 'one shared target':
+		assert int(n_row[0, 7]) >= 100 and n_row[0, 150] == 0 and (dy[0, 150] == 0).all() and dy[0, 7].abs().max() > 0
+	# one side only: the same numbers (d_x to the bit: one thread owns a row), nothing for the other side
+	dx1, none, _ = _knn1_bwd(x, y, xl, yl, w, need_y=False)
+	assert none is None and torch.equal(dx1, dx)
+	none, dy1, _ = _knn1_bwd(x, y, xl, yl, w, need_x=False)
+	assert none is None and ((dy1.double() - ry).abs() <= b_y).all()
