@@ -96,6 +96,8 @@ PROTOTYPES = {
 	'find_depth_loss_bwd': (c_int, [_P, _P, _P, _I, _I, c_int, c_float, c_float, _P, _P, _P, _P]),
 	'find_uv_sample': (c_int, [_P, _I, _I, _I, _P, _I, _P, _I, _I, _P, _P, _I, _I, _P, _P]),
 	'find_render_frags': (c_int, [POINTER(RenderParams), _I, _I, _I, _I, _P, _P, _P, _P]),
+	'find_uv_raster': (c_int, [_P, _I, _P, _I, _I, _I, _P, _P, _P]),
+	'find_uv_dilate_map': (c_int, [_P, _I, _I, _I, _P, _P]),
 	'find_adam_step': (c_int, [_I, _P, _P, _P, _P, _P, c_float, c_float, c_float, c_float, c_float, _I, _P]),
 	'find_adam_step_dev': (c_int, [_I, _P, _P, _P, _P, _P, c_float, c_float, c_float, c_float, c_float, _P, _P]),
 	'find_sgd_step': (c_int, [_I, _P, _P, _P, _P, c_float, c_float, c_float, c_float, c_int, c_int, _P]),

@@ -77,7 +77,7 @@ def eval_2d(model, dataset, image_size=128, nviews=1, batch_size=1, R=None, T=No
 
 def eval_3d(model, dataset, template_kp_idxs, samples=10000, z_cutoff=0.07, feet_per_call=16, render_correspondences=False, image_size=256,
 			return_per_foot=False, device='cuda', produce_spins=False, export_meshes=False, out_dir=None, spin_frames=250, spin_image_size=512,
-			spin_format='gif', surface=False):
+			spin_format='gif', surface=False, template_uvs=None, texture_size=1024, texture_pad=4):
 	"""model: a NeuralDisplacementField or a PCAModel whose validation latent tables are indexed by the dataset's item index (batch['idx']);
 	dataset: the validation Foot3DDataset, every foot with keypoints; template_kp_idxs: the template vertices of the keypoints (the
 	template foot's kp_idxs for a neural model, eval_metrics.PCA_KEYPOINTS for a PCAModel; eval_3d.py:132-138).  Ground-truth keypoints
@@ -97,11 +97,19 @@ def eval_3d(model, dataset, template_kp_idxs, samples=10000, z_cutoff=0.07, feet
 	depend on these keywords: no random number is drawn for them.
 	surface (not in the reference): eval_metrics.eval_3d_metrics(surface=True) -- 'Scan→pred (mm)', 'Pred→scan (mm)' and 'Surf (μm)' join the
 	returned metrics, with return_per_foot the second dict also holds 'scan_to_pred_mm' and 'pred_to_scan_mm' (N), and the heat maps of
-	produce_spins are coloured from vis.surface_errors (distances to the other surface) instead of vis.vertex_errors."""
+	produce_spins are coloured from vis.surface_errors (distances to the other surface) instead of vis.vertex_errors.
+	template_uvs (not in the reference): (verts_uvs (Vt,2), faces_uvs (F,3)), a UV atlas of the template's faces.  With export_meshes every
+	predicted foot is then also written as {n:02d}_pred_textured.obj / .mtl / .png beside the vertex-coloured one: the colour field baked
+	into a texture_size map with a gutter of texture_pad texels (find_amd.bake; a NeuralDisplacementField only).  None: nothing changes."""
 	if (produce_spins or export_meshes) and out_dir is None:
 		raise ValueError('find_amd.evaluate.eval_3d: produce_spins / export_meshes need out_dir')
 	keep_meshes = produce_spins or export_meshes
-	gt_meshes, pred_meshes = [], []
+	gt_meshes, pred_meshes, tex_meshes = [], [], []
+	bake_plan = None
+	if template_uvs is not None and export_meshes:
+		from . import bake
+		uvs = (template_uvs[0].to(device), template_uvs[1].to(device))
+		bake_plan = bake.plan(uvs[0], uvs[1], texture_size, pad=texture_pad)
 	collate = BatchCollator(device=device).collate_batches
 	loader = DataLoader(dataset, batch_size=feet_per_call, shuffle=False, collate_fn=collate)
 	kp_t = torch.as_tensor(template_kp_idxs, dtype=torch.long, device=device)
@@ -130,6 +138,9 @@ def eval_3d(model, dataset, template_kp_idxs, samples=10000, z_cutoff=0.07, feet
 				if keep_meshes:
 					gt_meshes += [gt[i] for i in range(len(gt))]
 					pred_meshes += [res['meshes'][i] for i in range(len(gt))]
+				if bake_plan is not None:
+					textured = bake.textured_meshes(model, bake_plan, uvs[0], uvs[1], batch, is_train=False)
+					tex_meshes += [textured[i] for i in range(len(gt))]
 				if render_correspondences:
 					images['gt'].append(renderer(gt, R, T, return_images=True, keypoints=gkp, keypoints_blend=True)['keypoints_blend'])
 					images['pred'].append(renderer(res['meshes'], R, T, return_images=True, keypoints=pkp, keypoints_blend=True)['keypoints_blend'])
@@ -148,6 +159,8 @@ def eval_3d(model, dataset, template_kp_idxs, samples=10000, z_cutoff=0.07, feet
 								 pred_all if surface else None)
 			if export_meshes:
 				written.setdefault('files', []).extend(_export(gt_meshes, pred_meshes, os.path.join(out_dir, 'meshes')))
+				for n, mesh in enumerate(tex_meshes):
+					written['files'].extend(bake.export_textured_obj(mesh, os.path.join(out_dir, 'meshes', f'{n:02d}_pred_textured.obj')))
 	finally:
 		model.train(was_training)
 	out = {k: float(metrics[k]) for k in ('Keypoint (mm)', f'Chamf z-cutoff {z_cutoff} (μm)', 'Chamf (μm)') + (('Scan→pred (mm)', 'Pred→scan (mm)', 'Surf (μm)') if surface else ())}

@@ -97,6 +97,24 @@ def template(n_verts=6890):
 	return ellipsoid_mesh(rings, segs)
 
 
+def face_atlas(n_faces, inset=0.1):
+	"""A UV atlas for ANY mesh of n_faces faces, the worst case for seams: every face gets a right triangle of its own, two per cell of
+	the smallest square grid that holds them, each `inset` of a cell away from the cell's border and 2^0.5 `inset` from its neighbour
+	across the diagonal (legs of 1 - 3 inset cells; inset < 1/3).  Face f sits in cell f // 2, cells row-major from (0, 0); all counter-
+	clockwise.  Returns verts_uvs (3 F, 2) float32 in (0, 1), faces_uvs (F, 3) int64 = arange(3 F).reshape(F, 3)."""
+	if not 0 <= inset < 1 / 3:
+		raise ValueError(f'face_atlas: 0 <= inset < 1/3 expected, got {inset}')
+	g = max(1, math.ceil(math.sqrt((n_faces + 1) // 2)))
+	s, d = 1.0 / g, inset / g
+	cell = np.arange(n_faces) // 2
+	org = np.stack([(cell % g) * s, (cell // g) * s], -1)[:, None, :]                  # (F, 1, 2)
+	lower = np.array([[d, d], [s - 2 * d, d], [d, s - 2 * d]])
+	upper = np.array([[s - d, s - d], [2 * d, s - d], [s - d, 2 * d]])
+	tri = np.where((np.arange(n_faces) % 2 == 0)[:, None, None], lower[None], upper[None])   # (F, 3, 2)
+	uv = (org + tri).reshape(-1, 2).astype(np.float32)
+	return torch.from_numpy(uv), torch.arange(3 * n_faces, dtype=torch.int64).reshape(n_faces, 3)
+
+
 def make_model(n_verts=6890, train_size=16, val_size=2, device='cuda', latent_size=100, nonzero_disp_head=True, **kw):
 	"""NeuralDisplacementField at FIND's training settings (train.py:148-157) with an ellipsoid template.
 	The last disp layer is re-drawn N(0, 0.01^2) (generator seed 1234) so the displacement head carries gradient:

@@ -624,6 +624,26 @@ int find_render_frags(const find_render_params* rp, int64_t n_meshes, int64_t n_
 					  int32_t* face_local, float* bary, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Baking into UV maps (bake.hip): the writing half of the UV textures above.  Not in the reference (it only ever reads scan textures).
+ * Texel (i, j) of an H x W map has its centre at (u, v) = (j / (W - 1), 1 - i / (H - 1)), row 0 the top of the image: the points
+ * find_uv_sample reads without interpolation.  2 <= H, W <= 4096.
+ * find_uv_raster: verts_uvs (n_uv_verts, 2), faces_uvs (n_faces, 3) int32 -> face (H, W) int32, the SMALLEST face index whose closed UV
+ *   triangle (either orientation) contains the texel's centre, -1 where none does, and bary (H, W, 3): the three edge functions of that face
+ *   at the centre over its signed area, in fp32 without contraction, recomputed from the winning face (0 where face is -1).  A face with an
+ *   index outside [0, n_uv_verts) or with a signed area that is 0 or NaN in fp32 covers nothing; UVs outside [0, 1] are legal and do not
+ *   wrap.  n_faces = 0 writes -1 / 0 everywhere (verts_uvs / faces_uvs may then be NULL).  A wave per face walks the face's clamped bounding
+ *   box in 8 x 8 tiles (boxes of many tiles are shared by 16 waves) and takes the minimum into `face` itself with integer atomics, which
+ *   is independent of their order: repeated calls are bit-identical; a texel per lane then writes -1 / bary.
+ * find_uv_dilate_map: face (H, W) as above -> src (H, W) int32, the flat index i * W + j of the texel to copy: a covered texel (face >= 0)
+ *   its own, an uncovered one that of the covered texel within Chebyshev distance `pad` with the smallest di^2 + dj^2 (ties: the smallest
+ *   flat index), -1 if there is none.  0 <= pad <= 16.  The gutter that keeps find_uv_sample's bilinear reads off the background.
+ * Neither uses a workspace or synchronises with the host.
+ * ---------------------------------------------------------------------------------------------- */
+int find_uv_raster(const float* verts_uvs, int64_t n_uv_verts, const int32_t* faces_uvs, int64_t n_faces, int64_t map_h, int64_t map_w,
+				   int32_t* face, float* bary, void* stream);
+int find_uv_dilate_map(const int32_t* face, int64_t map_h, int64_t map_w, int64_t pad, int32_t* src, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Per-vertex feature render (FootRenderer.forward(..., return_features=True, features=...), src/model/renderer.py:293-299).
  * Replaces FeatureShader.forward (renderer.py:74-105) on fragments['sil']: [P3D-recall] TexturesVertex(features).sample_textures
  * (interpolate_face_attributes with the clipped, perspective-correct barycentrics of the K = sil_faces_per_pixel, blurred pass) and
