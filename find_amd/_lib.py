@@ -94,6 +94,9 @@ PROTOTYPES = {
 	'find_depth_loss_ws_bytes': (c_int64, [_I, _I]),
 	'find_depth_loss_fwd': (c_int, [_P, _P, _P, _I, _I, c_int, c_float, c_float, _P, _P, _P, _I, _P]),
 	'find_depth_loss_bwd': (c_int, [_P, _P, _P, _I, _I, c_int, c_float, c_float, _P, _P, _P, _P]),
+	'find_ssim_ws_bytes': (c_int64, [_I, _I, _I, _I, c_int]),
+	'find_ssim_fwd': (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, c_float, c_int, _P, _P, _P, _P, _I, _P]),
+	'find_ssim_bwd': (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, c_float, c_int, _P, _P, _P, _P, _P]),
 	'find_uv_sample': (c_int, [_P, _I, _I, _I, _P, _I, _P, _I, _I, _P, _P, _I, _I, _P, _P]),
 	'find_render_frags': (c_int, [POINTER(RenderParams), _I, _I, _I, _I, _P, _P, _P, _P]),
 	'find_uv_raster': (c_int, [_P, _I, _P, _I, _I, _I, _P, _P, _P]),

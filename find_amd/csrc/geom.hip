@@ -56,6 +56,9 @@ __global__ void sample_fwd_kernel(const float* __restrict__ verts, const int32_t
 #pragma unroll
 	for (int c = 0; c < 3; ++c) {
 		const int vi = fp[c];
+		// a -1 row (the padding of a ragged batch, reached by given draws) or an index past the mesh: adds nothing and is never read through,
+		// as the backward below (it used to read the floats in front of the mesh's vertices: whatever the allocator had left there)
+		if ((unsigned)vi >= (unsigned)n_verts) continue;
 		const float3 v = ld3(vp + 3 * vi);
 		p.x += w[c] * v.x; p.y += w[c] * v.y; p.z += w[c] * v.z;
 		if (attr) {
@@ -82,7 +85,9 @@ __global__ void sample_bwd_kernel(const int32_t* __restrict__ faces, int64_t fac
 #pragma unroll
 	for (int c = 0; c < 3; ++c) {
 		const int vi = fp[c];
-		if (vi < 0) continue;   // a -1 row: sample_surface_kernel falls back to face 0 on a mesh without area, and face 0 of a mesh of padding only is one
+		// a -1 row (sample_surface_kernel falls back to face 0 on a mesh without area, and face 0 of a mesh of padding only is one) or an index
+		// past the mesh: nothing is added, as in the forward
+		if ((unsigned)vi >= (unsigned)n_verts) continue;
 		atomicAdd(dv + 3 * vi + 0, w[c] * gx);
 		atomicAdd(dv + 3 * vi + 1, w[c] * gy);
 		atomicAdd(dv + 3 * vi + 2, w[c] * gz);

@@ -11,6 +11,7 @@ sum of 0 -> nan)."""
 import torch
 
 from . import functional as FN
+from . import ssim as _ssim
 from .losses import point_mesh_distance, sample_points_from_meshes
 
 # template vertex ids of the six keypoints on the PCA foot model's mesh (reference src/cfg.yaml:11, read by eval_3d.py:137-138 and
@@ -179,3 +180,14 @@ def depth_error_mm(pred_rdrs, gt_rdrs, return_coverage=False):
 		seen = (gd > 0).reshape(N * M, H * Wd)
 		n_gt = (seen if weight is None else seen & (weight > 0)).sum(1).double()
 		return err, torch.where(n_gt > 0, per[:, 1] / n_gt.clamp(min=1), nan)
+
+
+def SSIM(gt, pred, gt_mask=None, pred_mask=None, border='valid'):
+	"""Structural similarity per image (not in the reference; find_amd.ssim.ssim, data_range 1): gt, pred (..., H, W, C) in [0, 1], C <= 4,
+	masks (..., H, W) or None, multiplied in.  Returns the float64 values of the images, leading dimensions folded; border 'valid' is
+	pytorch-msssim's convention (only windows inside the image count), 'same' that of 3DGS.  No gradient."""
+	_same_shape('SSIM', gt, pred)
+	with torch.no_grad():
+		_, per = _ssim.ssim(_f32(pred).detach(), _f32(gt).detach(), None if pred_mask is None else _f32(pred_mask).detach(),
+							None if gt_mask is None else _f32(gt_mask).detach(), data_range=1.0, border=border, return_per_image=True)
+	return per

@@ -14,7 +14,7 @@ import torch
 from torch.utils.data import DataLoader
 
 from .dataset import BatchCollator
-from .eval_metrics import depth_error_mm, eval_2d_metrics, eval_3d_metrics
+from .eval_metrics import SSIM, depth_error_mm, eval_2d_metrics, eval_3d_metrics
 from .renderer import FootRenderer
 from .structures import Meshes, TexturesVertex
 
@@ -31,7 +31,8 @@ def _marked_faces(textures):
 	return torch.argwhere(torch.all(fu == vu.shape[0] - 1, dim=-1)).flatten()
 
 
-def eval_2d(model, dataset, image_size=128, nviews=1, batch_size=1, R=None, T=None, feet_per_call=16, return_per_image=False, device='cuda', depth=False):
+def eval_2d(model, dataset, image_size=128, nviews=1, batch_size=1, R=None, T=None, feet_per_call=16, return_per_image=False, device='cuda', depth=False,
+			ssim=False):
 	"""model: a NeuralDisplacementField or a PCAModel whose validation latent tables are indexed by the dataset's item index (batch['idx'], as
 	eval_2d.py:28-35 samples them); dataset: the validation Foot3DDataset.  Views: linspace_views(nviews, dist=0.3, elev_min=-90,
 	elev_max=90) unless R, T are given; groups of `batch_size` consecutive views (nviews // batch_size of them per foot, the loop bound of
@@ -40,7 +41,10 @@ def eval_2d(model, dataset, image_size=128, nviews=1, batch_size=1, R=None, T=No
 	per-group float64 tensors (foot-major, nviews // batch_size groups per foot) as a second dict.
 	depth (not in the reference): two more columns from eval_metrics.depth_error_mm -- 'Depth (mm)', the mean absolute difference of the two
 	rendered depth maps where both see a surface, and 'Depth coverage', the share of the scan's pixels the prediction covers -- as means over
-	the images that have a value; the per-image tensors (one value per foot and view, NaN where there is none) join the second dict."""
+	the images that have a value; the per-image tensors (one value per foot and view, NaN where there is none) join the second dict.
+	ssim (not in the reference): two more columns from eval_metrics.SSIM (border 'valid') -- 'SSIM_A' on the images PSNR_A compares (the
+	prediction whitened under the GT's mask-out map, eval_2d.py:92-94) and 'SSIM_B' on those of PSNR_B (each image times its own mask > 0) --
+	per group the mean over its images, like IOU."""
 	renderer = FootRenderer(image_size=image_size, device=device)
 	if R is None:
 		R, T = renderer.linspace_views(nviews=nviews, dist=0.3, elev_min=-90, elev_max=90)
@@ -50,7 +54,7 @@ def eval_2d(model, dataset, image_size=128, nviews=1, batch_size=1, R=None, T=No
 	R, T = R[:n_used].to(device), T[:n_used].to(device)
 	collate = BatchCollator(device=device).collate_batches
 	loader = DataLoader(dataset, batch_size=feet_per_call, shuffle=False, collate_fn=lambda items: (collate(items), [_marked_faces(it['textures']) for it in items]))
-	per = {k: [] for k in METRICS + (('Depth (mm)', 'Depth coverage') if depth else ())}
+	per = {k: [] for k in METRICS + (('Depth (mm)', 'Depth coverage') if depth else ()) + (('SSIM_A', 'SSIM_B') if ssim else ())}
 	more = dict(return_depth=True) if depth else {}
 	was_training = model.training
 	model.eval()
@@ -68,11 +72,27 @@ def eval_2d(model, dataset, image_size=128, nviews=1, batch_size=1, R=None, T=No
 					err, cover = depth_error_mm(pred_rdrs, gt_rdrs, return_coverage=True)
 					per['Depth (mm)'].append(err)
 					per['Depth coverage'].append(cover)
+				if ssim:
+					for k, v in _ssim_columns(pred_rdrs, gt_rdrs, batch_size).items():
+						per[k].append(v)
 	finally:
 		model.train(was_training)
 	per = {k: torch.cat(v) for k, v in per.items()}
 	out = {k: float(v.nanmean() if k.startswith('Depth') else v.mean()) for k, v in per.items()}
 	return (out, per) if return_per_image else out
+
+
+def _ssim_columns(pred_rdrs, gt_rdrs, batch_size):
+	"""'SSIM_A' / 'SSIM_B' of renders of N feet x M views: float64, N * (M // batch_size) values, foot-major, a group's value the mean over
+	its images.  The images are those of eval_metrics.eval_2d_metrics' PSNR_A / PSNR_B, formed here (evaluation code, not a hot path)."""
+	gi, pi, gm, pm = gt_rdrs['image'], pred_rdrs['image'], gt_rdrs['mask'], pred_rdrs['mask']
+	hide = None if gt_rdrs.get('nothing_hidden', False) else gt_rdrs.get('mask_out_masks')
+	if hide is not None:
+		pi = torch.where(hide[..., None], torch.ones_like(pi), pi)
+		pm = torch.where(hide, torch.zeros_like(pm), pm)
+	a = SSIM(gi, pi)
+	b = SSIM(gi, pi, gt_mask=(gm > 0).float(), pred_mask=(pm > 0).float())
+	return {'SSIM_A': a.view(-1, batch_size).mean(1), 'SSIM_B': b.view(-1, batch_size).mean(1)}
 
 
 def eval_3d(model, dataset, template_kp_idxs, samples=10000, z_cutoff=0.07, feet_per_call=16, render_correspondences=False, image_size=256,

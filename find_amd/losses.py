@@ -13,6 +13,7 @@ import torch
 
 from . import functional as FN
 from . import functional_render as FR
+from . import ssim as _ssim
 from .structures import Meshes, TexturesUV, TexturesVertex
 
 nn = torch.nn
@@ -271,3 +272,22 @@ class DepthLoss(nn.Module):
 		"""pred, target (n_img, ...), positive where a surface is seen; weight of the same shape or None, without gradient:
 		sum w rho(pred - target) / max(sum w, 1e-12) over the pixels valid in both maps.  The gradient goes to pred only."""
 		return FN.depth_loss(pred, target, weight, kind=self.kind, delta=self.delta, trunc=self.trunc)
+
+
+class SSIMLoss(nn.Module):
+	"""1 - SSIM of two image batches (not in the reference, whose pixel loss is a mean squared error; the structural term of
+	differentiable-rendering losses): one HIP pass each way (find_amd.ssim.ssim)."""
+
+	def __init__(self, data_range=1.0, border='same'):
+		"""data_range: the span of the values (C1 = (0.01 data_range)^2, C2 = (0.03 data_range)^2); border 'same' (zero padding, every
+		pixel counts and gets a gradient) | 'valid' (only windows inside the image count)."""
+		super().__init__()
+		if border not in _ssim.BORDERS:
+			raise ValueError(f"SSIMLoss: border 'same' or 'valid', got {border!r}")
+		if not data_range > 0:
+			raise ValueError(f'SSIMLoss: data_range > 0 expected, got {data_range}')
+		self.data_range, self.border = float(data_range), border
+
+	def forward(self, pred, target, pred_mask=None, target_mask=None):
+		"""pred, target (..., H, W, C), C <= 4; masks (..., H, W) or None, multiplied in.  The gradient goes to pred and pred_mask only."""
+		return 1. - _ssim.ssim(pred, target, pred_mask, target_mask, data_range=self.data_range, border=self.border)

@@ -17,6 +17,7 @@ from .losses import (ContrastiveLoss, DisplacementLoss, MeshSmoothnessLoss, Norm
 					 TextureLossGTSpace)
 from .model import NeuralDisplacementField, PCAModel
 from .renderer import FootRenderer
+from .ssim import ssim
 
 nn = torch.nn
 
@@ -66,6 +67,7 @@ EVERY_EXTENSION_TERM = ALL_EXTENSION_TERMS + EXTENSION_TERMS_DEPTH
 # error against a silhouette MSE of 1e-2)
 EXTENSION_WEIGHTS = dict(weight_normal=1., weight_p2s=10000., weight_depth=100.)
 DEPTH_DEFAULTS = dict(depth_loss_kind='l1', depth_loss_delta=0.005, depth_trunc=0.02)
+PIX_DEFAULTS = dict(pix_ssim_lambda=0.)   # the share of 1 - SSIM in loss_pix (ModelWithLoss._raw_pix); 0: the reference's MSE alone
 
 
 # the GT render on a second stream beside the predicted one (ModelWithLoss._render_gt); FIND_OVERLAP_GT_RENDER=0 turns it off
@@ -266,7 +268,14 @@ class ModelWithLoss(nn.Module):
 	def _raw_pix(self, st):
 		# images are compared inside the silhouettes only (model.py:1101-1105): MSE(image * mask, gt image * gt mask), one pass each way
 		# (find_image_mse_*; CPU tensors raise there: no fallback)
-		return FN.image_mse(st.pred['image'], st.gt['image'], st.pred['mask'], st.gt['mask'])
+		lam = float(getattr(st.opts, 'pix_ssim_lambda', PIX_DEFAULTS['pix_ssim_lambda']))
+		if not 0. <= lam <= 1.:
+			raise ValueError(f'opts.pix_ssim_lambda: a share in [0, 1] expected, got {lam}')
+		mse = FN.image_mse(st.pred['image'], st.gt['image'], st.pred['mask'], st.gt['mask'])
+		if lam == 0.:
+			return mse
+		# the structural share (not in the reference): SSIM of the same masked images, one more pass each way (find_ssim_*)
+		return (1. - lam) * mse + lam * (1. - ssim(st.pred['image'], st.gt['image'], st.pred['mask'], st.gt['mask']))
 
 	def _raw_sil(self, st):
 		return FN.image_mse(st.pred['mask'], st.gt['mask'])

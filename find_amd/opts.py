@@ -36,6 +36,8 @@ class Opts:
 		# not in the reference: the depth term (ModelWithLoss.forward(depth=True)); metres, weight not tuned: about a millimetre of mean error
 		# against a silhouette MSE of 1e-2.  depth_loss_kind 'l1' | 'l2' | 'huber' (depth_loss_delta), depth_trunc: larger differences are left out
 		depth_loss=False, weight_depth=100., depth_loss_kind='l1', depth_loss_delta=0.005, depth_trunc=0.02,
+		# not in the reference: the structural share of the pixel term, loss_pix = (1 - l) MSE + l (1 - SSIM) (find_amd.ssim); 0: the MSE alone
+		pix_ssim_lambda=0.,
 	)
 
 	def __init__(self, **kw):

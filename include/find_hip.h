@@ -380,6 +380,8 @@ int find_pca_bwd(const float* coefs, int64_t V, int64_t B, const float* d_offset
  * (n_meshes, n_faces, 3); face_idx (n_meshes, n_samples) int32; uv (n_meshes, n_samples, 2).
  * out (n_meshes, n_samples, 3) = w0*v0 + w1*v1 + w2*v2,  (w0,w1,w2) = (1-sqrt(u), sqrt(u)(1-v), sqrt(u)v).
  * `attr` (optional, same layout as verts, n_attr channels=3) is sampled into attr_out with the same weights.
+ * A corner whose vertex index lies outside [0, n_verts) -- the -1 rows that pad a ragged batch's faces, when a given draw names one --
+ * adds nothing, forward and backward, and nothing is read through it.
  * ---------------------------------------------------------------------------------------------- */
 int find_sample_points_fwd(const float* verts, const int32_t* faces, int64_t faces_batch, const int32_t* face_idx,
 						   const float* uv, int64_t n_meshes, int64_t n_verts, int64_t n_faces, int64_t n_samples,
@@ -698,6 +700,29 @@ int find_depth_loss_fwd(const float* pred, const float* target, const float* wei
 						float* loss_out, double* per_image, void* ws, int64_t ws_bytes, void* stream);
 int find_depth_loss_bwd(const float* pred, const float* target, const float* weight, int64_t n_img, int64_t n_pix, int kind, float delta, float trunc,
 						const float* d_loss, const void* ws, float* d_pred, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * SSIM (ssim.hip): structural similarity (Wang et al. 2004) of two image batches, the definition of pytorch-msssim / 3DGS with
+ * data_range = L.  Not in the reference.  x, y (n_img, H, W, C) channel-last, C in 1 .. 4; xm, ym (n_img, H, W) or NULL (= 1);
+ * a = x * xm, b = y * ym.  Window: separable Gaussian, 11 taps, sigma 1.5, normalised in double, fp32 constants.  Per pixel and channel,
+ * with the window means m1 = E[a], m2 = E[b], s11 = E[a^2], s22 = E[b^2], s12 = E[ab], C1 = (0.01 L)^2, C2 = (0.03 L)^2:
+ *     ssim = (2 m1 m2 + C1)(2 (s12 - m1 m2) + C2) / ((m1^2 + m2^2 + C1)((s11 - m1^2) + (s22 - m2^2) + C2)).
+ * valid == 0 ("same"): the window is zero-padded at the border and an image's value is the mean over its H W C values; valid != 0: the mean
+ *   over the (H - 10)(W - 10) C values whose window lies inside the image (H, W >= 11).  Nothing outside the image is read.
+ * find_ssim_ws_bytes: want_grad == 0: the bytes of `ws` (a double per 16 x 16 tile); want_grad != 0: the bytes of `dmaps`
+ *   (n_img H W 3 C floats).  -1 for bad sizes (non-positive, C > 4, more than 65535 images, H or W above 32768).
+ * find_ssim_fwd: *mean_out = the mean over images of the per-image values; per_image (n_img) fp64 or NULL.  Moments and sums in double, a
+ *   partial per tile, added in a fixed order: no atomics, bit-identical on repeat.  dmaps or NULL: what the backward needs, (n_img, C, 3, H, W)
+ *   fp32: d ssim / d (m1, s11, s12) of every pixel scaled by 1 / (n_img * values per image), 0 where a pixel does not count; all of it is written.
+ * find_ssim_bwd: g: one fp32 on the device, d loss / d mean.  d_x (as x) and d_xm (as xm; needs xm), either may be NULL, are OVERWRITTEN,
+ *   every element: with d a(q) = sum_p w(p - q) [A1(p) + 2 a(q) A2(p) + b(q) A3(p)],  d_x = xm d a g,  d_xm = sum_c x_c d a_c g.  One launch, no
+ *   atomics.  y and ym receive no gradient.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t find_ssim_ws_bytes(int64_t n_img, int64_t H, int64_t W, int64_t C, int want_grad);
+int find_ssim_fwd(const float* x, const float* xm, const float* y, const float* ym, int64_t n_img, int64_t H, int64_t W, int64_t C, float L, int valid,
+				  float* mean_out, double* per_image, float* dmaps, void* ws, int64_t ws_bytes, void* stream);
+int find_ssim_bwd(const float* x, const float* xm, const float* y, const float* ym, int64_t n_img, int64_t H, int64_t W, int64_t C, float L, int valid,
+				  const float* g, const float* dmaps, float* d_x, float* d_xm, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Fused multi-tensor optimiser steps.  Replace torch.optim.Adam / torch.optim.SGD(momentum=0.9)
