@@ -97,6 +97,11 @@ PROTOTYPES = {
 	'find_ssim_ws_bytes': (c_int64, [_I, _I, _I, _I, c_int]),
 	'find_ssim_fwd': (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, c_float, c_int, _P, _P, _P, _P, _I, _P]),
 	'find_ssim_bwd': (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, c_float, c_int, _P, _P, _P, _P, _P]),
+	'find_plane_sections_ws_bytes': (c_int64, [_I, _I, _I, c_int]),
+	'find_plane_sections_fwd': (c_int, [_P, _P, _I, _P, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P]),
+	'find_plane_sections_bwd': (c_int, [_P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P]),
+	'find_extents_fwd': (c_int, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
+	'find_extents_bwd': (c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P]),
 	'find_uv_sample': (c_int, [_P, _I, _I, _I, _P, _I, _P, _I, _I, _P, _P, _I, _I, _P, _P]),
 	'find_render_frags': (c_int, [POINTER(RenderParams), _I, _I, _I, _I, _P, _P, _P, _P]),
 	'find_uv_raster': (c_int, [_P, _I, _P, _I, _I, _I, _P, _P, _P]),

@@ -11,6 +11,7 @@ sum of 0 -> nan)."""
 import torch
 
 from . import functional as FN
+from . import measure as _measure
 from . import ssim as _ssim
 from .losses import point_mesh_distance, sample_points_from_meshes
 
@@ -26,8 +27,34 @@ def keypoint_error_mm(pred_verts, template_kp_idxs, gt_kps):
 	return dists.mean() * 1e3
 
 
+def _foot_spec(measurements, who):
+	"""measurements: True (the default FootSpec) or a FootSpec."""
+	if measurements is True:
+		return _measure.FootSpec()
+	if not isinstance(measurements, _measure.FootSpec):
+		raise ValueError(f'find_amd.{who}: measurements must be True or a FootSpec (the spec of what to measure), got {measurements!r}')
+	return measurements
+
+
+def measurement_names(spec):
+	"""The table's keys of a FootSpec: 'Length (mm)', 'Width (mm)', 'Ball girth (mm)', ..."""
+	return tuple(n.replace('_', ' ').capitalize() + ' (mm)' for n in spec.names)
+
+
+def measurement_errors_mm(pred_meshes, gt_meshes, spec=None, return_per_foot=False):
+	"""Foot measurements of predictions against those of the scans (not in the reference; find_amd.measure.of_meshes on both):
+	{'Length (mm)', 'Width (mm)', 'Ball girth (mm)', 'Instep girth (mm)'} with the default FootSpec, each the mean over feet of
+	|pred - scan| x 1e3.  return_per_foot: also the two (N, M) tables in mm, the predictions' and the scans'.  No gradient."""
+	spec = _measure.FootSpec() if spec is None else _foot_spec(spec, 'eval_metrics.measurement_errors_mm')
+	with torch.no_grad():
+		pred = _measure.of_meshes(pred_meshes, spec)[0] * 1e3
+		gt = _measure.of_meshes(gt_meshes, spec)[0] * 1e3
+		out = dict(zip(measurement_names(spec), (pred - gt).abs().mean(0)))
+	return (out, pred, gt) if return_per_foot else out
+
+
 def eval_3d_metrics(pred_meshes, gt_meshes, pred_verts=None, template_kp_idxs=None, gt_kps=None, samples=10000, z_cutoff=0.07,
-					draws_gt=None, draws_pred=None, return_samples=False, surface=False, return_per_foot=False):
+					draws_gt=None, draws_pred=None, return_samples=False, surface=False, return_per_foot=False, measurements=None):
 	"""Returns {'Keypoint (mm)', 'Chamf z-cutoff <z> (um)', 'Chamf (um)'} as 0-d tensors (keypoints only when given); with return_samples
 	also (gt_pts, pred_pts), the (N,samples,3) surface samples the Chamfer terms were taken on (the per-vertex heat maps of eval_3d.py:171-178
 	read the predicted ones: no second draw).
@@ -35,7 +62,10 @@ def eval_3d_metrics(pred_meshes, gt_meshes, pred_verts=None, template_kp_idxs=No
 	'Scan→pred (mm)': the mean over feet of the mean unsquared distance of every scan vertex to the predicted surface, x 1e3; 'Pred→scan (mm)':
 	the same for the predicted vertices against the scan's surface; 'Surf (μm)': the symmetric mean squared distance of the very samples
 	'Chamf (μm)' used, x 1e6.  return_per_foot (with surface): a last value {'Scan→pred (mm)', 'Pred→scan (mm)'} of (N) tensors, a number per
-	foot."""
+	foot.
+	measurements (not in the reference; True or a measure.FootSpec): the keys of measurement_errors_mm join the result, and with
+	return_per_foot the last value also holds 'measure_pred_mm' and 'measure_gt_mm', the (N, M) tables.  No random number is drawn for them."""
+	spec = None if measurements is None or measurements is False else _foot_spec(measurements, 'eval_metrics.eval_3d_metrics')
 	with torch.no_grad():
 		gt_pts = sample_points_from_meshes(gt_meshes, num_samples=samples, draws=draws_gt)
 		pred_pts = sample_points_from_meshes(pred_meshes, num_samples=samples, draws=draws_pred)
@@ -64,7 +94,10 @@ def eval_3d_metrics(pred_meshes, gt_meshes, pred_verts=None, template_kp_idxs=No
 			s_pred, _, _ = point_mesh_distance(gt_pts, pred_meshes)
 			s_gt, _, _ = point_mesh_distance(pred_pts, gt_meshes)
 			out['Surf (μm)'] = (s_pred.mean(1) + s_gt.mean(1)).mean() * 1e6
-	ret = (out,) + (((gt_pts, pred_pts),) if return_samples else ()) + ((per_foot,) if surface and return_per_foot else ())
+		if spec is not None:
+			errs, per_foot['measure_pred_mm'], per_foot['measure_gt_mm'] = measurement_errors_mm(pred_meshes, gt_meshes, spec, return_per_foot=True)
+			out.update(errs)
+	ret = (out,) + (((gt_pts, pred_pts),) if return_samples else ()) + ((per_foot,) if (surface or spec is not None) and return_per_foot else ())
 	return ret if len(ret) > 1 else out
 
 

@@ -13,6 +13,7 @@ import torch
 
 from . import functional as FN
 from . import functional_render as FR
+from . import measure as _measure
 from . import ssim as _ssim
 from .structures import Meshes, TexturesUV, TexturesVertex
 
@@ -291,3 +292,31 @@ class SSIMLoss(nn.Module):
 	def forward(self, pred, target, pred_mask=None, target_mask=None):
 		"""pred, target (..., H, W, C), C <= 4; masks (..., H, W) or None, multiplied in.  The gradient goes to pred and pred_mask only."""
 		return 1. - _ssim.ssim(pred, target, pred_mask, target_mask, data_range=self.data_range, border=self.border)
+
+
+class MeasurementLoss(nn.Module):
+	"""Squared difference between a mesh's foot measurements (find_amd.measure.foot_measurements: length, width, girths) and given numbers
+	-- a tape's, where there is no scan (not in the reference).  The mean over feet and measurements, m^2; relative: of the difference
+	divided by the target, dimensionless.  The user composes it on model.get_meshes(...)['verts'] to refine latents with the existing
+	optimisers; it is no term of ModelWithLoss."""
+
+	def __init__(self, spec=None, relative=False):
+		super().__init__()
+		self.spec = _measure.FootSpec() if spec is None else spec
+		if not isinstance(self.spec, _measure.FootSpec):
+			raise ValueError(f'MeasurementLoss: spec must be a FootSpec, got {type(spec).__name__}')
+		self.relative = bool(relative)
+
+	def forward(self, verts, faces, target, v_len=None):
+		"""verts (N, V, 3), faces (F, 3) or (N, F, 3); target (N, M) in metres, columns as spec.names; a NaN entry is "not measured" and is
+		left out: the mean runs over the entries that count (0 when none does).  The gradient goes to the vertices."""
+		M = len(self.spec.names)
+		if target.dim() != 2 or target.shape != (verts.shape[0], M):
+			raise ValueError(f'MeasurementLoss: target ({verts.shape[0]}, {M}) for {self.spec.names} expected, got {tuple(target.shape)}')
+		values, _ = _measure.foot_measurements(verts, faces, self.spec, v_len)
+		target = target.to(values.device, values.dtype)
+		known = ~torch.isnan(target)
+		diff = torch.where(known, values - torch.where(known, target, values.detach()), torch.zeros_like(values))
+		if self.relative:
+			diff = diff / torch.where(known, target, torch.ones_like(target))
+		return (diff * diff).sum() / known.sum().clamp(min=1)

@@ -725,6 +725,46 @@ int find_ssim_bwd(const float* x, const float* xm, const float* y, const float* 
 				  const float* g, const float* dmaps, float* d_x, float* d_xm, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Foot measurements (measure.hip): sections of meshes by planes and extents along directions.  Not in the reference.
+ * verts (N, V, 3); faces (faces_batch, F, 3) int32, faces_batch 1 (shared) or N (per mesh, rows of -1 pad the shorter ones), as
+ * find_point_face_fwd; planes (planes_batch, P, 4) rows (nx, ny, nz, d), planes_batch 1 or N, 1 <= P <= 64.  The normal is taken as
+ * given (the caller normalises it).  The rule, per mesh and plane:
+ *   s = fmaf(nz, z, fmaf(ny, y, nx * x)) - d per vertex, "above" iff s >= 0; a face crosses iff its three vertices are not all on one side,
+ *   and then exactly two of its edges cross; on a crossing edge, lo the vertex below and hi the one above, t = s_lo / (s_lo - s_hi) (the
+ *   denominator is < 0) and p = fmaf(t, hi - lo, lo); the face contributes |p1 - p2|.  A face with a -1, an index outside [0, V) or a
+ *   repeated vertex contributes nothing.  So a closed mesh gives closed loops, an edge lying in the plane is counted once (by the face on
+ *   its lower side), a face lying in the plane contributes nothing, and a plane touching the mesh at one vertex gives crossing faces of
+ *   length 0.
+ * find_plane_sections_fwd: perimeter (N, P) fp32 the summed lengths, count (N, P) int32 the crossing faces.  One pass over the faces serves
+ *   all planes; fp32 per face, the sums in double: a partial per workgroup of 256 faces and plane, added by a second kernel in workgroup
+ *   order.  No float atomics: bit-identical on repeat, and a mesh's row does not depend on the rest of the batch.
+ *   ws: find_plane_sections_ws_bytes(N, F, P, 0) bytes, 8-byte aligned, free again when the call's work is done.
+ * find_plane_sections_bwd: from g (N, P): d_verts (N, V, 3) OVERWRITTEN, every element, the plain chain rule through p, t and s.  The face
+ *   pass writes the nine corner gradients of every face (summed over the planes in plane order; zeros for a face that crosses none), a
+ *   second kernel adds them per vertex through vf_off (faces_batch, V + 1) / vf_items (faces_batch, 3 F), the corner table of
+ *   find_vertex_normals_fwd, in the table's order.  d_offset (planes_batch, P) or NULL: the gradient of the offsets d, through a double
+ *   partial per workgroup, added in workgroup order and -- planes_batch 1 -- over the meshes in mesh order.  A segment of length 0 gives
+ *   a zero gradient.  The plane NORMALS receive no gradient.  ws: find_plane_sections_ws_bytes(N, F, P, 1) bytes (N F 9 floats and the
+ *   partials), 8-byte aligned.
+ * find_plane_sections_ws_bytes: -1 for bad sizes (N, F < 1, P outside 1 .. 64, N >= 65536, F >= 2^24, N F >= 2^32).
+ * find_extents_fwd: dirs (D, 3) fp32 on the device, 1 <= D <= 8; v_len (N) int32 or NULL (= V).  lo, hi (N, D): min and max of
+ *   fmaf(dz, z, fmaf(dy, y, dx * x)) over the first v_len[n] vertices, arg_lo, arg_hi (N, D) int32 where they are taken: among equal
+ *   values the smallest index.  v_len[n] == 0: 0, 0, -1, -1.  Rows at or past v_len[n] are never read.  A workgroup per mesh.
+ * find_extents_bwd: d_verts (N, V, 3) is ADDED INTO (zero-initialise it): g_lo[n, d] dir_d at arg_lo[n, d] and g_hi[n, d] dir_d at
+ *   arg_hi[n, d], a thread per mesh in the order lo_0, hi_0, lo_1, ...; g_lo or g_hi may be NULL.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t find_plane_sections_ws_bytes(int64_t N, int64_t F, int64_t P, int backward);
+int find_plane_sections_fwd(const float* verts, const int32_t* faces, int64_t faces_batch, const float* planes, int64_t planes_batch, int64_t N,
+							int64_t V, int64_t F, int64_t P, float* perimeter, int32_t* count, void* ws, int64_t ws_bytes, void* stream);
+int find_plane_sections_bwd(const float* verts, const int32_t* faces, int64_t faces_batch, const int32_t* vf_off, const int32_t* vf_items,
+							const float* planes, int64_t planes_batch, int64_t N, int64_t V, int64_t F, int64_t P, const float* g, float* d_verts,
+							float* d_offset, void* ws, int64_t ws_bytes, void* stream);
+int find_extents_fwd(const float* verts, const int32_t* v_len, const float* dirs, int64_t N, int64_t V, int64_t D, float* lo, float* hi,
+					 int32_t* arg_lo, int32_t* arg_hi, void* stream);
+int find_extents_bwd(const float* g_lo, const float* g_hi, const int32_t* arg_lo, const int32_t* arg_hi, const float* dirs, int64_t N,
+					 int64_t V, int64_t D, float* d_verts, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Fused multi-tensor optimiser steps.  Replace torch.optim.Adam / torch.optim.SGD(momentum=0.9)
  * as constructed by the reference (src/train/train.py:161-168) and stepped once per batch
  * (src/train/trainer.py:121-123).  `param`, `grad`, moment arrays: HOST arrays of n_tensors DEVICE pointers (fp32,
