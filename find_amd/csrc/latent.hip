@@ -170,9 +170,12 @@ extern "C" int find_latent_gather_many_bwd(int64_t n_tables, const float* const*
 // losses[k] = raw_k * opts.weight_k, loss = sum_k losses[k]   (reference src/model/model.py:1157-1163): one launch for all terms.
 namespace find {
 namespace latent {
+// (a bound of its own: MANY_MAX is the lookup's and stays 8; ModelWithLoss's registry has ten terms)
+constexpr int TERMS_MAX = 16;
+static_assert(TERMS_MAX <= 64, "weighted_terms_bwd_kernel: one thread per term in a 64-thread block");
 struct TermArgs {
-	const float* term[MANY_MAX];
-	float w[MANY_MAX];
+	const float* term[TERMS_MAX];
+	float w[TERMS_MAX];
 	int n;
 };
 __global__ void weighted_terms_fwd_kernel(const TermArgs a, float* __restrict__ scaled, float* __restrict__ total) {
@@ -194,7 +197,7 @@ __global__ void weighted_terms_bwd_kernel(const TermArgs a, const float* __restr
 }  // namespace find
 
 extern "C" int find_weighted_terms_fwd(int64_t n, const float* const* terms, const float* weights, float* scaled, float* total, void* stream) {
-	FIND_REQUIRE(n >= 1 && n <= latent::MANY_MAX && terms && weights && scaled && total, "find_weighted_terms_fwd: 1 .. %d terms, no NULL argument", latent::MANY_MAX);
+	FIND_REQUIRE(n >= 1 && n <= latent::TERMS_MAX && terms && weights && scaled && total, "find_weighted_terms_fwd: 1 .. %d terms, no NULL argument", latent::TERMS_MAX);
 	latent::TermArgs a;
 	memset(&a, 0, sizeof(a));
 	for (int64_t i = 0; i < n; ++i) {
@@ -208,7 +211,7 @@ extern "C" int find_weighted_terms_fwd(int64_t n, const float* const* terms, con
 }
 
 extern "C" int find_weighted_terms_bwd(int64_t n, const float* weights, const float* g_total, const float* g_scaled, float* d_terms, void* stream) {
-	FIND_REQUIRE(n >= 1 && n <= latent::MANY_MAX && weights && d_terms, "find_weighted_terms_bwd: 1 .. %d terms, no NULL argument", latent::MANY_MAX);
+	FIND_REQUIRE(n >= 1 && n <= latent::TERMS_MAX && weights && d_terms, "find_weighted_terms_bwd: 1 .. %d terms, no NULL argument", latent::TERMS_MAX);
 	FIND_REQUIRE(g_total || g_scaled, "find_weighted_terms_bwd: both upstream gradients NULL");
 	latent::TermArgs a;
 	memset(&a, 0, sizeof(a));

@@ -469,8 +469,13 @@ def latent_gather_many(tables, idxs):
 	return list(_LatentGatherMany.apply(len(tables), *tables, *idxs))
 
 
+# the most terms one weighted_terms call takes (latent.hip: TERMS_MAX -- not the latent lookup's MANY_MAX, which is 8)
+WEIGHTED_TERMS_MAX = 16
+
+
 class _WeightedTerms(torch.autograd.Function):
-	"""(sum_i w_i * term_i, [w_i * term_i]) for 0-dim device terms: ModelWithLoss's loss weighting (reference model.py:1157-1163)."""
+	"""(sum_i w_i * term_i, [w_i * term_i]) for up to WEIGHTED_TERMS_MAX = 16 0-dim device terms: ModelWithLoss's loss weighting (reference
+	model.py:1157-1163)."""
 
 	@staticmethod
 	def forward(ctx, weights, *terms):
@@ -500,9 +505,10 @@ class _WeightedTerms(torch.autograd.Function):
 
 
 def weighted_terms(terms, weights):
-	"""total = sum_i weights[i] * terms[i] (in order) and the list of the weighted terms, for 0-dim device tensors: one launch."""
-	if not 1 <= len(terms) <= 8 or len(terms) != len(weights):
-		raise ValueError('find_amd.weighted_terms: 1 .. 8 terms, one weight each')
+	"""total = sum_i weights[i] * terms[i] (in order) and the list of the weighted terms, for 1 .. WEIGHTED_TERMS_MAX (16) 0-dim device
+	tensors: one launch."""
+	if not 1 <= len(terms) <= WEIGHTED_TERMS_MAX or len(terms) != len(weights):
+		raise ValueError(f'find_amd.weighted_terms: 1 .. {WEIGHTED_TERMS_MAX} terms, one weight each')
 	total, scaled = _WeightedTerms.apply(tuple(float(w) for w in weights), *terms)
 	return total, [scaled[i] for i in range(len(terms))]
 

@@ -245,7 +245,7 @@ int find_latent_gather_many_bwd(int64_t n_tables, const float* const* d_outs, co
 
 /* ------------------------------------------------------------------------------------------------
  * Loss weighting: scaled[i] = *terms[i] * weights[i], *total = sum_i scaled[i] in term order (ModelWithLoss.forward,
- * src/model/model.py:1157-1163: losses[k] = raw * opts.weight_k, loss = sum).  terms: HOST array of n <= 8 device scalars; weights:
+ * src/model/model.py:1157-1163: losses[k] = raw * opts.weight_k, loss = sum).  terms: HOST array of 1 <= n <= 16 device scalars; weights:
  * host floats; scaled (n) and total: device.  Backward: d_terms[i] = weights[i] * (*g_total + g_scaled[i]); either upstream may be NULL.
  * ---------------------------------------------------------------------------------------------- */
 int find_weighted_terms_fwd(int64_t n, const float* const* terms, const float* weights, float* scaled, float* total, void* stream);

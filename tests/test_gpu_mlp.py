@@ -554,6 +554,100 @@ def test_latent_gather_many_and_weighted_terms():
 	assert [round(r.grad.item(), 4) for r in raws] == [20000.0, 2000.0, 3.0]
 
 
+@pytest.mark.parametrize('n,zero_at', [(1, None), (8, 3), (9, 5), (16, 0)])
+def test_weighted_terms_against_float64(n, zero_at):
+	"""functional.weighted_terms at 1, 8, 9 and 16 terms (8 was the old bound, 16 is the new one) against the float64 restatement of the
+	float32 inputs: raw values from 1e-3 to 3, weights from 1 to 1e4 and one weight of exactly zero.
+
+	Bounds, u = 2^-24 the unit roundoff of float32:
+	* scaled[i] is ONE fp32 product: exactly float32(float32(raw_i) * float32(w_i)) -- numpy's float32 product rounds the same way.
+	* total = fl(...fl(fl(v_0 + v_1) + v_2)... + v_{n-1}) with v_i = scaled[i] >= 0: v_i carries one rounding of its product (<= u v_i), each of
+	  the n - 1 additions one rounding of a partial sum that is <= S = sum_i raw_i w_i (all addends are >= 0): |total - S| <= u S + (n - 1) u S
+	  to first order = n u S, and u S < ulp(S) because ulp(S) = 2^(e - 23) for 2^e <= S < 2^(e + 1).  So: n ulps of the float64 sum.
+	* backward: d_i = fl(w_i * fl(g_total + g_scaled_i)).  Through total alone (g_total = 1) and through one scaled[k] alone (g_scaled = e_k) the
+	  sum and the product are exact: d is exactly w_i, resp. w_k e_k -- a term that gets no gradient gets exactly zero.  Through
+	  2 * total + scaled[k] the sums 2 and 3 are exact and the product rounds once: within u of the float64 value (asserted at 2 u: one
+	  rounding each for the sum and the product, whatever the upstream values)."""
+	from find_amd import functional as FN
+	rng = np.random.default_rng(100 + n)
+	raw = np.exp(rng.uniform(np.log(1e-3), np.log(3.), n)).astype(np.float32)
+	w = np.exp(rng.uniform(0., np.log(1e4), n)).astype(np.float32)
+	raw[0], raw[-1], w[-1], w[n // 2] = 1e-3, 3., 1e4, 1.   # the ends of both spans (n = 1: raw 3, weight 1)
+	if zero_at is not None:
+		w[zero_at] = 0.
+	k = n // 3   # the term whose scaled output gets a gradient of its own
+	view_at = min(1, n - 1)   # this term is a 0-dim view into a larger tensor, as per[0] of a per-foot loss would be (offset 2 floats)
+	scaled64 = raw.astype(np.float64) * w.astype(np.float64)
+	S = scaled64.sum()
+
+	def terms():
+		per = torch.tensor([7., 7., float(raw[view_at]), 7.], device='cuda', requires_grad=True)
+		own = [torch.tensor(float(v), device='cuda', requires_grad=True) for v in raw]
+		return per, own, [per[2] if i == view_at else t for i, t in enumerate(own)]
+
+	def grads(per, own):
+		g = [(per.grad[2] if i == view_at else t.grad) for i, t in enumerate(own)]
+		assert per.grad[0].item() == 0 and per.grad[1].item() == 0 and per.grad[3].item() == 0 and own[view_at].grad is None
+		return np.array([x.item() for x in g], dtype=np.float64)
+
+	per, own, ts = terms()
+	total, scaled = FN.weighted_terms(ts, [float(x) for x in w])
+	assert total.dtype == torch.float32 and total.dim() == 0 and len(scaled) == n and all(s.dim() == 0 for s in scaled)
+	got = np.array([s.item() for s in scaled], dtype=np.float32)
+	np.testing.assert_array_equal(got, raw * w)   # (float32 * float32 in numpy: the one rounded product)
+	ulp = float(np.spacing(np.float32(S)))
+	err = abs(float(total.item()) - S)
+	print(f'weighted_terms n={n}: total {total.item()!r} float64 {S!r}: {err / ulp:.2f} ulp (bar {n})')
+	assert err <= n * ulp, (err / ulp, n)
+	if zero_at is not None:
+		assert got[zero_at] == 0.
+	# ---- backward, three ways
+	w64 = w.astype(np.float64)
+	total.backward(retain_graph=True)
+	np.testing.assert_array_equal(grads(per, own), w64)
+	per, own, ts = terms()
+	total, scaled = FN.weighted_terms(ts, [float(x) for x in w])
+	scaled[k].backward()
+	want = np.zeros(n)
+	want[k] = w64[k]
+	np.testing.assert_array_equal(grads(per, own), want)   # every other term: exactly zero
+	per, own, ts = terms()
+	total, scaled = FN.weighted_terms(ts, [float(x) for x in w])
+	(2 * total + scaled[k]).backward()
+	want = w64 * (2. + (np.arange(n) == k))
+	g = grads(per, own)
+	worst = float(np.max(np.abs(g - want) / np.maximum(want, 1e-30)))
+	print(f'weighted_terms n={n}: 2 * total + scaled[{k}]: worst relative gradient error {worst:.2e} (bar {2. ** -23:.2e})')
+	assert np.all(np.abs(g - want) <= 2. ** -23 * want)
+	if zero_at is not None:
+		assert g[zero_at] == 0.
+
+
+def test_weighted_terms_refuses_17_terms_without_a_launch():
+	"""One more than the bound, through the C interface with real device pointers: the library's error code, and nothing written."""
+	import ctypes
+	from find_amd import _lib
+	from find_amd import functional as FN
+	L = _lib.lib()
+	n = FN.WEIGHTED_TERMS_MAX + 1
+	assert n == 17
+	ts = [torch.ones((), device='cuda') for _ in range(n)]
+	out = torch.full((n + 1,), -5., device='cuda')
+	w = (ctypes.c_float * n)(*[1.] * n)
+	torch.cuda.synchronize()
+	rc = L.find_weighted_terms_fwd(n, FN._ptr_array(ts), w, _lib.ptr(out), ctypes.c_void_p(out.data_ptr() + 4 * n), _lib.current_stream(out.device))
+	assert rc == -1 and '1 .. 16 terms' in L.find_last_error().decode()
+	g = torch.ones((), device='cuda')
+	rc = L.find_weighted_terms_bwd(n, w, _lib.ptr(g), None, _lib.ptr(out), _lib.current_stream(out.device))
+	assert rc == -1 and '1 .. 16 terms' in L.find_last_error().decode()
+	torch.cuda.synchronize()
+	assert (out == -5.).all()
+	with pytest.raises(ValueError, match=r'1 \.\. 16 terms'):
+		FN.weighted_terms(ts, [1.] * n)
+	total, scaled = FN.weighted_terms(ts[:16], [1.] * 16)
+	assert total.item() == 16.
+
+
 @pytest.mark.parametrize('n_feet,variant', [(16, 'bf16x3'), (16, 'dw4'), (1, 'dw4'), (16, 'dw2_whole_file'), (16, 'fp16')])
 def test_backward_is_bit_reproducible_under_co_residence_stress(n_feet, variant):
 	"""The stress configuration that made round 1's rare fault happen in every pass (mlp.hip, 'Co-residence fault'): the slab reduces are

@@ -1209,6 +1209,7 @@ def _rules_step(i):
 
 # Every term this setup can feed: the eight below.  Left out: cont_pose (needs pose codes in the batch: test_gpu_contrastive.py's composition) and
 # restyle_perc_cluster (needs an encoder network of the caller's: test_gpu_part_loss.py's stub); their ops have cases of their own above.
+# (Eight was also the most terms weighted_terms took; it takes 16 now, and test_gpu_all_terms.py holds the step with all ten terms to its parts.)
 case('ModelWithLoss step, chamf + smooth + texture + sil + pix + normal + p2s + depth',
 	 ['_MLP', '_Render', '_RenderFeatures', '_Chamfer', '_SmoothLoss', '_MaskedMSE', '_ImageMSE', '_Register', '_LatentGatherMany', '_WeightedTerms', '_PointFace', '_DepthMap',
 	  '_DepthLoss', '_NormalLoss', '_VertexNormals'],
