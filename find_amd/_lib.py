@@ -2,7 +2,7 @@
 missing or a call fails, a RuntimeError is raised."""
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_float, c_int, c_int16, c_int32, c_int64, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float,c_int, c_int16, c_int32, c_int64, c_void_p
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, 'lib', 'libfind_hip.so')
@@ -102,6 +102,11 @@ PROTOTYPES = {
 	'find_plane_sections_bwd': (c_int, [_P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P]),
 	'find_extents_fwd': (c_int, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
 	'find_extents_bwd': (c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P]),
+	'find_align_ws_bytes': (c_int64, [_I, _I]),
+	'find_align_fit': (c_int, [_P, _P, _P, _P, _I, _I, c_int, c_int, _P, _P, _P, _P, _P, _I, _P]),
+	'find_icp_ws_bytes': (c_int64, [_I, _I, _I]),
+	'find_icp_run': (c_int, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _I, c_double, c_int, c_double, c_float, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+							 _P, _I, _P]),
 	'find_uv_sample': (c_int, [_P, _I, _I, _I, _P, _I, _P, _I, _I, _P, _P, _I, _I, _P, _P]),
 	'find_render_frags': (c_int, [POINTER(RenderParams), _I, _I, _I, _I, _P, _P, _P, _P]),
 	'find_uv_raster': (c_int, [_P, _I, _P, _I, _I, _I, _P, _P, _P]),

@@ -10,6 +10,7 @@ in float64 on the device; the scalar functions return float32 0-d tensors like t
 sum of 0 -> nan)."""
 import torch
 
+from . import align as _align
 from . import functional as FN
 from . import measure as _measure
 from . import ssim as _ssim
@@ -54,7 +55,7 @@ def measurement_errors_mm(pred_meshes, gt_meshes, spec=None, return_per_foot=Fal
 
 
 def eval_3d_metrics(pred_meshes, gt_meshes, pred_verts=None, template_kp_idxs=None, gt_kps=None, samples=10000, z_cutoff=0.07,
-					draws_gt=None, draws_pred=None, return_samples=False, surface=False, return_per_foot=False, measurements=None):
+					draws_gt=None, draws_pred=None, return_samples=False, surface=False, return_per_foot=False, align=None, measurements=None):
 	"""Returns {'Keypoint (mm)', 'Chamf z-cutoff <z> (um)', 'Chamf (um)'} as 0-d tensors (keypoints only when given); with return_samples
 	also (gt_pts, pred_pts), the (N,samples,3) surface samples the Chamfer terms were taken on (the per-vertex heat maps of eval_3d.py:171-178
 	read the predicted ones: no second draw).
@@ -64,7 +65,14 @@ def eval_3d_metrics(pred_meshes, gt_meshes, pred_verts=None, template_kp_idxs=No
 	'Chamf (μm)' used, x 1e6.  return_per_foot (with surface): a last value {'Scan→pred (mm)', 'Pred→scan (mm)'} of (N) tensors, a number per
 	foot.
 	measurements (not in the reference; True or a measure.FootSpec): the keys of measurement_errors_mm join the result, and with
-	return_per_foot the last value also holds 'measure_pred_mm' and 'measure_gt_mm', the (N, M) tables.  No random number is drawn for them."""
+	return_per_foot the last value also holds 'measure_pred_mm' and 'measure_gt_mm', the (N, M) tables.  No random number is drawn for them.
+	align (not in the reference; None, 'rigid' or 'similarity'): errors after alignment, for a prediction that is right up to a rigid motion
+	(or a similarity).  The prediction is moved onto the scan by find_amd.align.iterative_closest_point from the very predicted samples to
+	the very scan samples the Chamfer term drew -- no further random number is drawn -- and 'Chamf aligned (μm)' is the Chamfer term of the
+	moved samples; with keypoints 'Keypoint aligned (mm)' is the keypoint error of the predicted keypoints under the same transform.  With
+	return_per_foot the last value also holds 'align_R' (N, 3, 3), 'align_T' (N, 3), 'align_s' (N) and 'align_rmse' (N).  None changes nothing."""
+	if align not in (None, 'rigid', 'similarity'):
+		raise ValueError(f"find_amd.eval_metrics.eval_3d_metrics: align must be None, 'rigid' or 'similarity', got {align!r}")
 	spec = None if measurements is None or measurements is False else _foot_spec(measurements, 'eval_metrics.eval_3d_metrics')
 	with torch.no_grad():
 		gt_pts = sample_points_from_meshes(gt_meshes, num_samples=samples, draws=draws_gt)
@@ -97,7 +105,14 @@ def eval_3d_metrics(pred_meshes, gt_meshes, pred_verts=None, template_kp_idxs=No
 		if spec is not None:
 			errs, per_foot['measure_pred_mm'], per_foot['measure_gt_mm'] = measurement_errors_mm(pred_meshes, gt_meshes, spec, return_per_foot=True)
 			out.update(errs)
-	ret = (out,) + (((gt_pts, pred_pts),) if return_samples else ()) + ((per_foot,) if (surface or spec is not None) and return_per_foot else ())
+		if align is not None:
+			sol = _align.iterative_closest_point(pred_pts, gt_pts, estimate_scale=align == 'similarity')
+			out['Chamf aligned (μm)'] = FN.chamfer_distance(gt_pts, sol.Xt)[0] * 1e6
+			if template_kp_idxs is not None:
+				kp = torch.as_tensor(template_kp_idxs, device=pred_verts.device, dtype=torch.long)
+				out['Keypoint aligned (mm)'] = torch.norm(sol.RTs.apply(pred_verts[:, kp]) - gt_kps, dim=-1).mean() * 1e3
+			per_foot.update(align_R=sol.RTs.R, align_T=sol.RTs.T, align_s=sol.RTs.s, align_rmse=sol.rmse)
+	ret = (out,) + (((gt_pts, pred_pts),) if return_samples else ()) + ((per_foot,) if (surface or spec is not None or align is not None) and return_per_foot else ())
 	return ret if len(ret) > 1 else out
 
 

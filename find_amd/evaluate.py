@@ -97,7 +97,7 @@ def _ssim_columns(pred_rdrs, gt_rdrs, batch_size):
 
 def eval_3d(model, dataset, template_kp_idxs, samples=10000, z_cutoff=0.07, feet_per_call=16, render_correspondences=False, image_size=256,
 			return_per_foot=False, device='cuda', produce_spins=False, export_meshes=False, out_dir=None, spin_frames=250, spin_image_size=512,
-			spin_format='gif', surface=False, template_uvs=None, texture_size=1024, texture_pad=4, measurements=False):
+			spin_format='gif', surface=False, template_uvs=None, texture_size=1024, texture_pad=4, align=None, measurements=False):
 	"""model: a NeuralDisplacementField or a PCAModel whose validation latent tables are indexed by the dataset's item index (batch['idx']);
 	dataset: the validation Foot3DDataset, every foot with keypoints; template_kp_idxs: the template vertices of the keypoints (the
 	template foot's kp_idxs for a neural model, eval_metrics.PCA_KEYPOINTS for a PCAModel; eval_3d.py:132-138).  Ground-truth keypoints
@@ -123,7 +123,12 @@ def eval_3d(model, dataset, template_kp_idxs, samples=10000, z_cutoff=0.07, feet
 	into a texture_size map with a gutter of texture_pad texels (find_amd.bake; a NeuralDisplacementField only).  None: nothing changes.
 	measurements (not in the reference; True or a find_amd.measure.FootSpec): eval_metrics.eval_3d_metrics(measurements=...) -- 'Length (mm)',
 	'Width (mm)', 'Ball girth (mm)' and 'Instep girth (mm)' (the spec's names) join the returned metrics, each the mean over feet of
-	|prediction - scan|; with return_per_foot the second dict also holds 'measure_pred_mm' and 'measure_gt_mm' (N, M).  False: nothing changes."""
+	|prediction - scan|; with return_per_foot the second dict also holds 'measure_pred_mm' and 'measure_gt_mm' (N, M).  False: nothing changes.
+	align (not in the reference; None, 'rigid' or 'similarity'): eval_metrics.eval_3d_metrics(align=...) -- 'Chamf aligned (μm)' and 'Keypoint
+	aligned (mm)', the errors after the prediction has been moved onto the scan by ICP on the Chamfer term's own samples, join the returned
+	metrics; with return_per_foot the second dict also holds 'align_R', 'align_T', 'align_s' and 'align_rmse'.  None: nothing changes."""
+	if align not in (None, 'rigid', 'similarity'):
+		raise ValueError(f"find_amd.evaluate.eval_3d: align must be None, 'rigid' or 'similarity', got {align!r}")
 	spec = _foot_spec(measurements, 'evaluate.eval_3d') if measurements is not False and measurements is not None else None
 	if (produce_spins or export_meshes) and out_dir is None:
 		raise ValueError('find_amd.evaluate.eval_3d: produce_spins / export_meshes need out_dir')
@@ -174,9 +179,10 @@ def eval_3d(model, dataset, template_kp_idxs, samples=10000, z_cutoff=0.07, feet
 			pred_all = Meshes(pred_v, pred_f)
 			got = eval_3d_metrics(pred_all, gt_all, pred_verts=pred_verts, template_kp_idxs=kp_t, gt_kps=gt_kps, samples=samples, z_cutoff=z_cutoff,
 								  return_samples=True, **(dict(surface=True) if surface else {}), **(dict(measurements=spec) if spec is not None else {}),
-								  **(dict(return_per_foot=True) if surface or spec is not None else {}))
+								  **(dict(align=align) if align is not None else {}),
+								  **(dict(return_per_foot=True) if surface or spec is not None or align is not None else {}))
 			metrics, (_, pred_pts) = got[0], got[1]
-			surf_per_foot = got[2] if surface or spec is not None else {}
+			surf_per_foot = got[2] if surface or spec is not None or align is not None else {}
 			per_foot = torch.norm(pred_verts[:, kp_t] - gt_kps, dim=-1) * 1e3
 			written = {}
 			if produce_spins:
@@ -189,7 +195,7 @@ def eval_3d(model, dataset, template_kp_idxs, samples=10000, z_cutoff=0.07, feet
 	finally:
 		model.train(was_training)
 	out = {k: float(metrics[k]) for k in ('Keypoint (mm)', f'Chamf z-cutoff {z_cutoff} (μm)', 'Chamf (μm)') + (('Scan→pred (mm)', 'Pred→scan (mm)', 'Surf (μm)') if surface else ())
-		   + (measurement_names(spec) if spec is not None else ())}
+		   + (measurement_names(spec) if spec is not None else ()) + (('Chamf aligned (μm)', 'Keypoint aligned (mm)') if align is not None else ())}
 	if not (return_per_foot or render_correspondences or keep_meshes):
 		return out
 	extra = dict(written)
@@ -199,6 +205,8 @@ def eval_3d(model, dataset, template_kp_idxs, samples=10000, z_cutoff=0.07, feet
 			extra['scan_to_pred_mm'], extra['pred_to_scan_mm'] = surf_per_foot['Scan→pred (mm)'], surf_per_foot['Pred→scan (mm)']
 		if spec is not None:
 			extra['measure_pred_mm'], extra['measure_gt_mm'] = surf_per_foot['measure_pred_mm'], surf_per_foot['measure_gt_mm']
+		if align is not None:
+			extra.update({k: surf_per_foot[k] for k in ('align_R', 'align_T', 'align_s', 'align_rmse')})
 	if render_correspondences:
 		extra.update({k: torch.cat(v) for k, v in images.items()})
 	return out, extra

@@ -765,6 +765,49 @@ int find_extents_bwd(const float* g_lo, const float* g_hi, const int32_t* arg_lo
 					 int64_t V, int64_t D, float* d_verts, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Rigid and similarity alignment of point clouds (align.hip).  Not in the reference; stands in for
+ * pytorch3d.ops.corresponding_points_alignment and iterative_closest_point.  Row vectors: x' = s (x @ R) + t, R (n, 3, 3) row-major.
+ * No allocation, no host synchronisation and no float atomics in either call; every sum is taken in double in a fixed order (256 pairs per
+ * workgroup: lanes by butterfly, waves in wave order, workgroups in workgroup order), so two runs agree bit for bit and a cloud's row does
+ * not depend on the rest of the batch.  status (n) int32: 0, or the sum of FIND_ALIGN_MAX_ITERATIONS (1) and FIND_ALIGN_DEGENERATE (2).
+ * find_align_fit: Umeyama / Kabsch on the pairs (x[n, i], y[n, i]), i < len[n] (len NULL: p_max), of weight w[n, i] (w NULL: 1; a weight
+ *   that is not > 0 and finite counts as 0, and such a pair is never read).  The minimiser of sum w |s (x @ R) + t - y|^2: the centred
+ *   cross-covariance H = sum w (x - mu_x)^T (y - mu_y) = U D V^T (3 x 3 SVD by one-sided Jacobi rotations in double), R = U diag(1, 1, e) V^T
+ *   with e = det(U) det(V) -- e = 1 if allow_reflection --, s = trace(D diag(1, 1, e)) / sum w |x - mu_x|^2 if estimate_scale, else 1,
+ *   t = mu_y - s mu_x R.  R, t, s are rounded to fp32 once, at the end.  Fewer than 3 pairs of positive weight, or an H whose second singular
+ *   value is <= 1e-12 of its first (rank < 2; with estimate_scale also an x without spread): identity, t = 0, s = 1, status 2; never NaN.
+ *   Precision: the moments are taken about the cloud's first pair (x[n, 0], y[n, 0]) as pivots, in double, so the covariance loses
+ *   |mu - pivot|^2 / sigma^2 * 2^-53 relative, whatever the cloud's distance from the origin.
+ *   ws: find_align_ws_bytes(n, p_max) bytes, 8-byte aligned (-1 for bad sizes: n, p_max < 1, n >= 65536, p_max >= 2^24, n p_max >= 2^31).
+ * find_icp_run: trimmed ICP from x (n, p1_max, 3) / x_len to y (n, p2_max, 3) / y_len, the whole loop enqueued on `stream` by one call.
+ *   From init_R (n, 3, 3), init_t (n, 3), init_s (n) -- all three or all NULL (identity) --, max_iterations + 1 rounds of:
+ *     apply    xt = fmaf(s, fmaf(x2, R[2][j], fmaf(x1, R[1][j], x0 * R[0][j])), t[j]) in fp32 (rows past x_len: zeros);
+ *     match    find_nn_fwd(xt, y): dist = d2, idx (lowest index on ties; padding rows as find_nn_fwd leaves them: 0 / -1);
+ *     select   (trim > 0) tau = the exact k-th smallest d2 among the cloud's m = x_len valid queries, k = m - floor(trim m), by a radix
+ *              select over the floats' bit patterns; a pair is USED iff d2 <= tau (ties at tau all count) and d2 <= max_dist^2
+ *              (fp32 product; max_dist = INFINITY: no limit).  trim == 0: tau = +inf;
+ *     solve    rmse = sqrt(sum d2 / count) over the used pairs (0 without any) -- the rmse of the transform the match used.  A cloud
+ *              whose |rmse_prev - rmse| <= rel_tol rmse_prev has converged: its transform is left alone from then on (the later rounds
+ *              still match it: wasted but harmless, there is no host round trip to skip them).  Otherwise, except in the last round,
+ *              the fit above over (x[i], y[idx[i]]) of the used pairs replaces the transform: every round solves for the ABSOLUTE
+ *              transform from the original x, so once the correspondences stop changing, transform and rmse repeat bit for bit.
+ *              A degenerate fit leaves the transform, freezes the cloud the same way and sets status bit 2.
+ *   So the returned xt, dist, idx, tau, used and rmse belong to the returned R, t, s.  iterations (n): the updates applied; status: 0 converged,
+ *   1 stopped at max_iterations without, 2 degenerate.  used (n) int32: the pairs of the last round's sums.  Reflections are never allowed.
+ *   ws: find_icp_ws_bytes(n, p1_max, p2_max) bytes, 8-byte aligned.  0 <= max_iterations <= 10000, rel_tol >= 0, 0 <= trim < 1, max_dist > 0.
+ * ---------------------------------------------------------------------------------------------- */
+#define FIND_ALIGN_MAX_ITERATIONS 1
+#define FIND_ALIGN_DEGENERATE 2
+int64_t find_align_ws_bytes(int64_t n, int64_t p_max);
+int find_align_fit(const float* x, const float* y, const int32_t* len, const float* w, int64_t n, int64_t p_max, int estimate_scale,
+				   int allow_reflection, float* R, float* t, float* s, int32_t* status, void* ws, int64_t ws_bytes, void* stream);
+int64_t find_icp_ws_bytes(int64_t n, int64_t p1_max, int64_t p2_max);
+int find_icp_run(const float* x, const int32_t* x_len, const float* y, const int32_t* y_len, int64_t n, int64_t p1_max, int64_t p2_max,
+				 const float* init_R, const float* init_t, const float* init_s, int64_t max_iterations, double rel_tol, int estimate_scale,
+				 double trim, float max_dist, float* R, float* t, float* s, float* rmse, int32_t* iterations, int32_t* status, float* xt,
+				 float* dist, int32_t* idx, float* tau, int32_t* used, void* ws, int64_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Fused multi-tensor optimiser steps.  Replace torch.optim.Adam / torch.optim.SGD(momentum=0.9)
  * as constructed by the reference (src/train/train.py:161-168) and stepped once per batch
  * (src/train/trainer.py:121-123).  `param`, `grad`, moment arrays: HOST arrays of n_tensors DEVICE pointers (fp32,
