@@ -120,6 +120,10 @@ PROTOTYPES = {
 	'find_pca_fwd': (c_int, [_P, _I, _I, _P, _I, _P, _P]),
 	'find_pca_bwd_ws_bytes': (c_int64, [_I, _I, _I]),
 	'find_pca_bwd': (c_int, [_P, _I, _I, _P, _I, _P, _P, _I, _P]),
+	'find_skin_fwd_ws_bytes': (c_int64, [_I, _I, _I, _I, _I]),
+	'find_skin_fwd': (c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _I, _P]),
+	'find_skin_bwd_ws_bytes': (c_int64, [_I, _I, _I, _I, _I]),
+	'find_skin_bwd': (c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P, _I, _P]),
 	'find_sample_points_fwd': (c_int, [_P, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
 	'find_sample_points_bwd': (c_int, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
 	'find_face_areas': (c_int, [_P, _P, _I, _I, _I, _I, _P, _P]),

@@ -33,8 +33,9 @@ def _marked_faces(textures):
 
 def eval_2d(model, dataset, image_size=128, nviews=1, batch_size=1, R=None, T=None, feet_per_call=16, return_per_image=False, device='cuda', depth=False,
 			ssim=False):
-	"""model: a NeuralDisplacementField or a PCAModel whose validation latent tables are indexed by the dataset's item index (batch['idx'], as
-	eval_2d.py:28-35 samples them); dataset: the validation Foot3DDataset.  Views: linspace_views(nviews, dist=0.3, elev_min=-90,
+	"""model: a NeuralDisplacementField, a PCAModel or a SkinnedModel -- any model with latent_vectors_val and get_meshes_from_batch -- whose
+	validation latent tables are indexed by the dataset's item index (batch['idx'], as eval_2d.py:28-35 samples them); dataset: the
+	validation Foot3DDataset.  Views: linspace_views(nviews, dist=0.3, elev_min=-90,
 	elev_max=90) unless R, T are given; groups of `batch_size` consecutive views (nviews // batch_size of them per foot, the loop bound of
 	eval_2d.py:86).  Feet are rendered `feet_per_call` at a time; the metrics are per image sums composed in float64, so the result does
 	not depend on that choice.  Returns {'MSE', 'PSNR_A', 'PSNR_B', 'PSNR_C', 'IOU'} as floats, and with return_per_image also the
@@ -98,9 +99,11 @@ def _ssim_columns(pred_rdrs, gt_rdrs, batch_size):
 def eval_3d(model, dataset, template_kp_idxs, samples=10000, z_cutoff=0.07, feet_per_call=16, render_correspondences=False, image_size=256,
 			return_per_foot=False, device='cuda', produce_spins=False, export_meshes=False, out_dir=None, spin_frames=250, spin_image_size=512,
 			spin_format='gif', surface=False, template_uvs=None, texture_size=1024, texture_pad=4, align=None, measurements=False):
-	"""model: a NeuralDisplacementField or a PCAModel whose validation latent tables are indexed by the dataset's item index (batch['idx']);
+	"""model: a NeuralDisplacementField, a PCAModel or a SkinnedModel -- any model with latent_vectors_val and get_meshes_from_batch -- whose
+	validation latent tables are indexed by the dataset's item index (batch['idx']);
 	dataset: the validation Foot3DDataset, every foot with keypoints; template_kp_idxs: the template vertices of the keypoints (the
-	template foot's kp_idxs for a neural model, eval_metrics.PCA_KEYPOINTS for a PCAModel; eval_3d.py:132-138).  Ground-truth keypoints
+	template foot's kp_idxs for a neural model, eval_metrics.PCA_KEYPOINTS for a PCAModel, the caller's own ids for a SkinnedModel;
+	eval_3d.py:132-138).  Ground-truth keypoints
 	are the scan's vertices at its kp_idxs, predicted ones the prediction's vertices at template_kp_idxs.  Predictions are made
 	`feet_per_call` at a time; the metrics are taken once over all feet, as eval_3d.py:146-161 does, so the keypoint table does not depend
 	on that choice and the Chamfer terms draw their samples as one eval_3d_metrics call over all feet would.

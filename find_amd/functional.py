@@ -695,6 +695,14 @@ def pca_offsets(coefs, shapevec):
 	return _PCAOffsets.apply(coefs, shapevec)
 
 
+# ----------------------------------------------------------------------------------------------- skinned foot model
+def linear_blend_skinning(consts, pose, betas, trans, return_joints=False):
+	"""Vertices (N, V, 3) of a skinned model from axis-angle poses (N, 3J), shape coefficients (N, B) and translations (N, 3): HIP forward and
+	backward (find_skin_fwd / find_skin_bwd).  The op lives in find_amd.skinning (its workspaces come from _ws here); see there."""
+	from . import skinning
+	return skinning.linear_blend_skinning(consts, pose, betas, trans, return_joints=return_joints)
+
+
 # ----------------------------------------------------------------------------------------------- surface sampling
 def _faces_i32(faces):
 	f = faces if faces.dtype == torch.int32 else faces.to(torch.int32)

@@ -654,3 +654,214 @@ class PCAModel(Model):
 		out = super().to(device)
 		self._rebuild_template_mesh()
 		return out
+
+
+def _skin_arrays(data, num_betas, dtype=np.float32):
+	"""The constants of a skinned model from the arrays of a STAR / SUPR style file (SkinnedModel.load), as `dtype` / int tensors on the CPU:
+	v_template (V, 3), dirs (V, B + P, 3), J0 (J, 3), JS (J, B, 3), weights (V, J), parent (J) int32, faces (F, 3) int64.  The joint
+	regressor is folded through the template and the shape directions here, in float64: J0 = Jreg v_template, JS = Jreg shapedirs.
+	Anything whose shape is not one of the layouts named in SkinnedModel.load is refused with that shape in the message."""
+	def need(key):
+		if key not in data:
+			raise ValueError(f'SkinnedModel: the file has no `{key}` (keys: {sorted(data)})')
+		a = data[key]
+		return a.detach().cpu().numpy() if torch.is_tensor(a) else a
+
+	def bad(key, a, want):
+		return ValueError(f'SkinnedModel: `{key}` has shape {tuple(a.shape)}; expected {want}')
+
+	vt = np.asarray(need('v_template'), dtype=np.float64)
+	if vt.ndim != 2 or vt.shape[1] != 3 or vt.shape[0] < 1:
+		raise bad('v_template', vt, '(V, 3)')
+	V = vt.shape[0]
+	w = np.asarray(need('weights'), dtype=np.float64)
+	if w.ndim != 2 or w.shape[0] != V or w.shape[1] < 1:
+		raise bad('weights', w, f'({V}, J)')
+	J = w.shape[1]
+	sd = np.asarray(need('shapedirs'), dtype=np.float64)
+	if sd.ndim != 3 or sd.shape[:2] != (V, 3) or sd.shape[2] < num_betas or num_betas < 1:
+		raise bad('shapedirs', sd, f'({V}, 3, >= num_betas = {num_betas})')
+	sd = sd[:, :, :num_betas]
+	pd = np.asarray(need('posedirs'), dtype=np.float64)
+	if pd.ndim == 2 and pd.shape[0] == 3 * V:
+		pd = pd.reshape(V, 3, -1)
+	if pd.ndim != 3 or pd.shape[:2] != (V, 3) or pd.shape[2] not in (4 * J, 4 * (J - 1)):
+		raise bad('posedirs', pd, f'({V}, 3, P) or ({3 * V}, P) with P = 4 J = {4 * J} or 4 (J - 1) = {4 * (J - 1)} quaternion features')
+	jr = need('J_regressor')
+	if hasattr(jr, 'toarray'):   # scipy.sparse
+		jr = jr.toarray()
+	jr = np.asarray(jr, dtype=np.float64)
+	if jr.shape == (3 * J, 3 * V):
+		# the regressor acting on the flattened vertices (rows 3j + c, columns 3v + c): it must be a per-coordinate copy of one (J, V) matrix
+		small = jr[0::3, 0::3]
+		if not np.array_equal(jr, np.kron(small, np.eye(3))):
+			raise ValueError(f'SkinnedModel: `J_regressor` has shape {tuple(jr.shape)} but is not kron(R, I3) of a ({J}, {V}) regressor R')
+		jr = small
+	if jr.shape != (J, V):
+		raise bad('J_regressor', jr, f'({J}, {V}) or ({3 * J}, {3 * V})')
+	kt = np.asarray(need('kintree_table'))
+	if kt.shape != (2, J):
+		raise bad('kintree_table', kt, f'(2, {J})')
+	parent = kt[0].astype(np.int64)
+	parent[(parent < 0) | (parent >= J)] = -1   # (the published files mark the root with 2^32 - 1)
+	for j in range(J):
+		if parent[j] >= j or (j == 0 and parent[j] != -1):
+			raise ValueError(f'SkinnedModel: `kintree_table` puts joint {j} before its parent {parent[j]}; parents must precede their children')
+	f = np.asarray(need('f'))
+	if f.ndim != 2 or f.shape[1] != 3 or (f.size and (f.min() < 0 or f.max() >= V)):
+		raise bad('f', f, f'(F, 3) with vertex ids below {V}')
+	dirs = np.concatenate([sd, pd], axis=2).transpose(0, 2, 1)   # (V, B + P, 3)
+	J0 = jr @ vt
+	JS = np.einsum('jv,vcb->jbc', jr, sd)
+	t32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=dtype))
+	return dict(v_template=t32(vt), dirs=t32(dirs), J0=t32(J0), JS=t32(JS), weights=t32(w), parent=torch.from_numpy(parent.astype(np.int32)),
+				faces=torch.from_numpy(f.astype(np.int64)))
+
+
+class SkinnedModel(Model):
+	"""Articulated foot model, the third model FIND is compared with (reference model.py:658-799, SUPRModel): SMPL-family linear blend
+	skinning with quaternion pose correctives as STAR / SUPR publish it, then the learned similarity registration.  The reference calls a
+	submodule for the skinning; here it is find_skin_fwd / find_skin_bwd (FN.linear_blend_skinning), the registration find_register_fwd / bwd.
+	Tables, batch keys and parameter groups are upstream's: pose (3J, zeros), betas (B), trans (3, -mean(v_template)) and reg (9), each
+	_train and _val; main = betas_train + pose_train, val = betas_val + pose_val, reg = both regs, latent = betas and pose of both splits,
+	trans in none.  Not upstream's: reg_init defaults to the identity (upstream hard-codes a start rotation for SUPR; align.init_registration
+	finds one: reg / reg_val / template_verts / template_faces are there for it), the loop that caps the open ankle is an argument of load
+	(cap_loops), and a checkpoint carries the model's constants, so loading one needs no path to the model file."""
+	CONSTS = ('v_template', 'dirs', 'J0', 'JS', 'weights', 'parent')
+	TABLES = ('pose', 'betas', 'trans', 'reg')
+
+	def __init__(self, *args, train_size=None, val_size=None, device='cuda', num_betas=10, reg_init=None, **kwargs):
+		super().__init__()
+		reg_init = [0.] * 6 + [1.] * 3 if reg_init is None else [float(x) for x in reg_init]
+		if len(reg_init) != 9:
+			raise ValueError(f'SkinnedModel: reg_init must have 9 entries (translation, euler XYZ, scale), got {len(reg_init)}')
+		self.params = dict(train_size=train_size, val_size=val_size, num_betas=num_betas, reg_init=reg_init)
+		self.train_size, self.val_size, self.num_betas, self.reg_init = train_size, val_size, num_betas, reg_init
+		# set by configure_template
+		self.template_verts = self.template_faces = self.template_mesh = None
+		for k in self.CONSTS:
+			setattr(self, k, None)
+		for k in self.TABLES:
+			setattr(self, f'{k}_train', None)
+			setattr(self, f'{k}_val', None)
+		self.latent_vectors_train, self.latent_vectors_val = [], []
+		self.configure_params()
+
+	@property
+	def reg(self):
+		"""reg_train under the name the other models (and align.init_registration) use; reg_val is upstream's name already."""
+		return self.reg_train
+
+	def configure_params(self):
+		"""Parameter groups read by train.py:161-168 (model.py:718-722)."""
+		self.main_params = make_params_list(self.betas_train, self.pose_train)
+		self.val_params = make_params_list(self.betas_val, self.pose_val)
+		self.reg_params = make_params_list(self.reg_train, self.reg_val)
+		self.latent_params = make_params_list(self.betas_train, self.betas_val, self.pose_train, self.pose_val)
+
+	def _rebuild_template_mesh(self):
+		if self.template_verts is not None:
+			self.template_mesh = Meshes(verts=self.template_verts.data, faces=self.template_faces.data[0])
+			self._no_verts = torch.zeros_like(self.template_verts.data)
+
+	def _apply(self, fn, *args, **kwargs):
+		out = super()._apply(fn, *args, **kwargs)
+		self._rebuild_template_mesh()
+		return out
+
+	def get_meshes(self, poses=None, betas=None, trans=None, reg=None, return_joints=False, **kwargs):
+		"""dict(meshes, verts) for poses (N, 3J), betas (N, B), translations (N, 3) and registrations (N, 9) or None (model.py:726-744).  Every
+		other keyword is accepted and ignored, as upstream.  The texture is a constant grey.  return_joints (not upstream): also `joints`
+		(N, J, 3), the posed joints before the registration, detached."""
+		X, joints = FN.linear_blend_skinning(self, poses, betas, trans, return_joints=True)
+		if reg is not None:
+			X = FN.register_points(self._no_verts, X, reg)
+		meshes = extend_template(self.template_mesh, N=X.shape[0]).update_padded(X)
+		meshes.textures = TexturesVertex(torch.full(X.shape, 0.5, dtype=torch.float32, device=X.device))
+		res = dict(meshes=meshes, verts=X)
+		if return_joints:
+			res['joints'] = joints
+		return res
+
+	def get_meshes_from_batch(self, batch, is_train=True, **kwargs):
+		sfx = 'train' if is_train else 'val'
+		return self.get_meshes(poses=batch[f'pose_{sfx}'], betas=batch[f'betas_{sfx}'], trans=batch[f'trans_{sfx}'], reg=batch.get(f'reg_{sfx}', None))
+
+	def forward(self, *args, **kwargs):
+		raise NotImplementedError('SkinnedModel has no field to query: it is evaluated through get_meshes / get_meshes_from_batch (the texture loss, '
+								  'which queries a colour field, does not apply to it)')
+
+	def configure_template(self, state_dict, device='cuda'):
+		"""The model's constants, the centred rest mesh as template_verts / template_faces, and the eight latent tables in upstream's order
+		(model.py:690-709)."""
+		for k in self.CONSTS:
+			t = state_dict[k]
+			setattr(self, k, nn.Parameter((t.to(torch.int32) if k == 'parent' else t.float()).to(device), requires_grad=False))
+		V, J = self.weights.shape
+		B = self.JS.shape[1]
+		if B != self.num_betas:
+			raise ValueError(f'SkinnedModel: the constants hold {B} shape directions, num_betas is {self.num_betas}')
+		trans_init = -self.v_template.data.mean(dim=0)
+		self.template_verts = nn.Parameter((self.v_template.data + trans_init).unsqueeze(0), requires_grad=False)
+		self.template_faces = nn.Parameter(state_dict['template_faces'].to(device), requires_grad=False)
+		self._rebuild_template_mesh()
+		trans_init = trans_init.cpu().numpy()
+		reg_init = np.array(self.reg_init)
+		for sfx, size, tables in (('train', self.train_size, self.latent_vectors_train), ('val', self.val_size, self.latent_vectors_val)):
+			del tables[:]
+			made = dict(pose=LatentVector(size, vec_size=3 * J, name=f'pose_{sfx}', device=device),
+						betas=LatentVector(size, vec_size=B, name=f'betas_{sfx}', device=device),
+						trans=LatentVector(size, vec_size=3, name=f'trans_{sfx}', device=device, init_values=trans_init),
+						reg=LatentVector(size, vec_size=9, name=f'reg_{sfx}', device=device, init_values=reg_init))
+			for k in self.TABLES:
+				setattr(self, f'{k}_{sfx}', made[k])
+				tables.append(made[k])
+		self.configure_params()
+
+	@classmethod
+	def from_arrays(cls, data, device='cuda', num_betas=10, cap_loops=None, **kwargs):
+		"""A model from the arrays of a STAR / SUPR style file (the keys: load).  cap_loops: ordered vertex loops, each closed with a fan of
+		triangles (loop[0], loop[i], loop[i + 1]) appended to the faces -- upstream's cap over the open ankle (model.py:713-716)."""
+		sd = _skin_arrays(data, num_betas)
+		faces = sd.pop('faces')
+		V = sd['v_template'].shape[0]
+		for loop in (cap_loops or []):
+			loop = [int(i) for i in loop]
+			if len(loop) < 3 or min(loop) < 0 or max(loop) >= V:
+				raise ValueError(f'SkinnedModel: a cap loop needs at least 3 vertex ids below {V}, got {len(loop)} ids in [{min(loop, default=0)}, {max(loop, default=0)}]')
+			faces = torch.cat([faces, torch.tensor([[loop[0], b, c] for b, c in zip(loop[1:], loop[2:])], dtype=torch.int64)], dim=0)
+		sd['template_faces'] = faces.unsqueeze(0)
+		kwargs.pop('opts', None)
+		model = cls(device=device, num_betas=num_betas, **kwargs)
+		model.configure_template(sd, device=device)
+		return model
+
+	@classmethod
+	def load(cls, file, device='cuda', opts=None, num_betas=10, cap_loops=None, **kwargs):
+		"""file: .npz (plain arrays), .npy holding a pickled dict (the format SUPR is distributed in) or a .pth checkpoint of a fitted
+		SkinnedModel.  Arrays read from a model file: v_template (V, 3), shapedirs (V, 3, >= num_betas), posedirs (V, 3, P) or (3V, P)
+		with P = 4J or 4(J-1), J_regressor (J, V) or (3J, 3V), dense or scipy-sparse, weights (V, J), kintree_table (2, J) with the
+		parents in row 0 (any out-of-range value marks the root; parents must precede their children, else ValueError) and f (F, 3)."""
+		ext = os.path.splitext(file)[-1]
+		if ext == '.pth':
+			data = torch.load(file, map_location=device, weights_only=False)
+			params, sd = dict(data['params']), data['state_dict']
+			skip_latents = opts is not None and getattr(opts, 'dont_load_latents', False)
+			if skip_latents:
+				params['train_size'], params['val_size'] = kwargs.get('train_size', 1), kwargs.get('val_size', 1)
+				sd = {k: v for k, v in sd.items() if k not in {f'{t}_{s}.data' for t in cls.TABLES for s in ('train', 'val')}}
+			model = cls(**params, device=device)
+			model.configure_template(sd, device=device)
+			model.load_state_dict(sd, strict=False)
+			return model
+		if ext == '.npz':
+			with np.load(file, allow_pickle=False) as z:
+				data = {k: z[k] for k in z.files}
+		elif ext == '.npy':
+			data = np.load(file, allow_pickle=True)   # (a pickled dict: the one place that unpickles a model file)
+			if not (isinstance(data, np.ndarray) and data.dtype == object and data.shape == ()) or not isinstance(data.item(), dict):
+				raise ValueError(f'SkinnedModel: {file} does not hold a dict (got {type(data).__name__} of shape {getattr(data, "shape", None)})')
+			data = data.item()
+		else:
+			raise NotImplementedError(f'Filetype `{ext}` for a skinned model not understood')
+		return cls.from_arrays(data, device=device, num_betas=num_betas, cap_loops=cap_loops, **kwargs)

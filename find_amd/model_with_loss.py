@@ -15,13 +15,13 @@ from . import functional as FN
 from . import losses as _losses
 from .losses import (ContrastiveLoss, DisplacementLoss, MeshSmoothnessLoss, NormalLoss, RestylePerceptualLoss, SilhouetteLoss, SurfaceDistanceLoss,
 					 TextureLossGTSpace)
-from .model import NeuralDisplacementField, PCAModel
+from .model import NeuralDisplacementField, PCAModel, SkinnedModel
 from .renderer import FootRenderer
 from .ssim import ssim
 
 nn = torch.nn
 
-model_zoo = dict(neural=NeuralDisplacementField, pca=PCAModel)
+model_zoo = dict(neural=NeuralDisplacementField, pca=PCAModel, skinned=SkinnedModel)
 
 OUT_OF_SCOPE_FLAGS = {
 	'vgg_perc': 'perceptual / restyle losses are out of scope (SURVEY.md §2 #4)',
@@ -159,8 +159,9 @@ def _third_stream(device):
 def model_class_from_opts(opts):
 	kind = getattr(opts, 'model_type', 'neural')
 	if kind not in model_zoo:
-		raise NotImplementedError(f"model_type '{kind}': only the neural displacement field and the PCA baseline are on the hot path (the SUPR "
-								  'and vertex-feature baselines are out of scope, SURVEY.md §2 #7-9)')
+		raise NotImplementedError(f"model_type '{kind}': the neural displacement field, the PCA baseline and the skinned model ('skinned': the "
+								  "algorithm behind upstream's 'supr', loaded from the model's own arrays) are on the hot path; upstream's SUPR "
+								  'submodule wrapper and the vertex-feature baseline are out of scope (SURVEY.md §2 #7-9)')
 	return model_zoo[kind]
 
 
@@ -374,10 +375,10 @@ class ModelWithLoss(nn.Module):
 		for name, why in OUT_OF_SCOPE_FLAGS.items():
 			if given[name]:
 				raise NotImplementedError(why)
-		if texture and isinstance(self.model, PCAModel):
+		if texture and isinstance(self.model, (PCAModel, SkinnedModel)):
 			# (upstream ends in an AttributeError inside TextureLossGTSpace, losses.py:22-57)
-			raise NotImplementedError('texture=True: the texture loss queries the model\'s colour field, and the PCA model (model_type=\'pca\') has '
-									  'none; switch the texture term off for it')
+			raise NotImplementedError('texture=True: the texture loss queries the model\'s colour field, and the PCA and skinned models (model_type=\'pca\' '
+									  '/ \'skinned\') have none; switch the texture term off for them')
 		if restyle_perc_cluster:
 			self._require_part_loss(opts, None if self.restyle_perc_loss is None else self.restyle_perc_loss.encoder)
 		# The contrastive pose term (model.py:1042-1049): a batch without pose rows is an error whatever its size; one scan gives no term.

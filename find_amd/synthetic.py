@@ -134,6 +134,48 @@ def make_model(n_verts=6890, train_size=16, val_size=2, device='cuda', latent_si
 	return m
 
 
+SKIN_CHAINS = {'line': lambda j: j - 1, 'star': lambda j: 0, 'tree': lambda j: (j - 1) // 2}
+
+
+def skinned_model(V=1002, J=5, B=10, chain='line', feature_joints='all', seed=0):
+	"""A random but well-formed skinned model (SMPL-family linear blend skinning, model.SkinnedModel) as a dict of numpy arrays under the keys
+	of the published STAR / SUPR files: v_template (V, 3) -- the template(V) foot where that grid exists, else a uniform ellipsoid of V
+	vertices (below 4 vertices: points and no faces) --, shapedirs (V, 3, B), posedirs (V, 3, P) with P = 4 J (feature_joints 'all') or
+	4 (J - 1) ('nonroot'), J_regressor (J, V) with at most 8 non-zeros per row, each row summing to 1, weights (V, J) non-negative with
+	at most 4 non-zeros per row, each row summing to 1, kintree_table (2, J) with the parents in row 0 (the root's: 2^32 - 1, as published;
+	chain 'line': j - 1, 'star': 0, 'tree': (j - 1) // 2) and f (F, 3)."""
+	if chain not in SKIN_CHAINS or feature_joints not in ('all', 'nonroot'):
+		raise ValueError(f'skinned_model: chain {chain!r} / feature_joints {feature_joints!r} not understood')
+	rng = np.random.RandomState(seed)
+	axes = np.array([0.12, 0.045, 0.04])
+	if V in TEMPLATE_GRIDS or (MESH_KIND == 'uniform' and V >= 4):
+		v, f = template(V)
+		v, f = v.numpy().astype(np.float64), f.numpy()
+	elif V >= 4:
+		v, f = uniform_sphere_mesh(V)
+		v, f = v.numpy().astype(np.float64) * axes, f.numpy()
+	else:
+		v, f = rng.uniform(-1, 1, (V, 3)) * axes, np.zeros((0, 3), np.int64)
+	# joints spread along the foot's long axis; each regressed from the vertices nearest to its seed
+	seeds = np.stack([np.linspace(-0.1, 0.1, J) if J > 1 else np.zeros(1), rng.uniform(-0.01, 0.01, J), rng.uniform(-0.01, 0.01, J)], -1)
+	reg = np.zeros((J, V))
+	for j in range(J):
+		near = np.argsort(((v - seeds[j]) ** 2).sum(-1), kind='stable')[:min(8, V)]
+		w = rng.uniform(0.2, 1.0, len(near))
+		reg[j, near] = w / w.sum()
+	joints = reg @ v
+	d2 = ((v[:, None] - joints[None]) ** 2).sum(-1)                       # (V, J)
+	near = np.argsort(d2, axis=1, kind='stable')[:, :min(4, J)]
+	w = np.exp(-np.take_along_axis(d2, near, 1) / 0.03 ** 2) + 1e-3
+	weights = np.zeros((V, J))
+	np.put_along_axis(weights, near, w / w.sum(1, keepdims=True), 1)
+	P = 4 * J if feature_joints == 'all' else 4 * (J - 1)
+	parents = np.array([2 ** 32 - 1] + [SKIN_CHAINS[chain](j) for j in range(1, J)], dtype=np.uint32)
+	return dict(v_template=v.astype(np.float32), shapedirs=(rng.randn(V, 3, B) * 0.004).astype(np.float32),
+				posedirs=(rng.randn(V, 3, P) * 0.002).astype(np.float32), J_regressor=reg.astype(np.float32), weights=weights.astype(np.float32),
+				kintree_table=np.stack([parents, np.arange(J, dtype=np.uint32)]), f=f.astype(np.int64))
+
+
 def latents(n_feet, latent_size=100, seed=0, device='cuda'):
 	"""shape / tex / pose codes ~ N(0, 0.1^2); reg: t~U(-0.01,0.01), euler~U(-0.1,0.1), S~U(0.9,1.1)."""
 	g = torch.Generator().manual_seed(seed)

@@ -373,6 +373,31 @@ int find_pca_bwd(const float* coefs, int64_t V, int64_t B, const float* d_offset
 				 void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Skinned foot model (src/model/model.py:726-727, SUPRModel.get_meshes: self.supr_model(poses, betas, trans)): SMPL-family linear blend
+ * skinning with quaternion pose correctives, as STAR / SUPR publish it.  Per foot n and joint j, th = pose[n, 3j:3j+3], a = |th|:
+ *   R_j = exp([th]x) (Rodrigues);  q_j = ((sin(a/2) / a) th, cos(a/2) - 1);  c = [betas | q_0.. (P = 4J) or q_1.. (P = 4(J-1))]
+ *   v_posed = v_template + sum_k dirs[:, k] c_k;  Jn = J0 + JS . betas  (the joint regressor folded through the shape directions)
+ *   G_0 = [R_0 | Jn_0], G_j = G_parent(j) o [R_j | Jn_j - Jn_parent(j)];  A_j = [G_j.R | G_j.t - G_j.R Jn_j]
+ *   out[n, v] = sum_j weights[v, j] (A_j.R v_posed + A_j.t) + trans[n]
+ * The angle is |th| itself, not STAR's |th + 1e-8|; power series below a = 1, so values and derivatives are exact at th = 0.
+ * v_template (V, 3); dirs (V, B+P, 3), shape directions first (the layout of pca_coefs); J0 (J, 3); JS (J, B, 3); weights (V, J);
+ * parent (J) int32, parent[j] < j, anything else (as the root's -1) read as "no parent"; pose (n_feet, 3J); betas (n_feet, B);
+ * trans (n_feet, 3); out (n_feet, V, 3); joints NULL or (n_feet, J, 3), the posed joints G_j.t.
+ * 1 <= J <= 128, P = 4J or 4(J-1), 3(B+P) padded + J within 9216 floats, B + P + 12J <= 3072, 1 <= V < 2^29, 1 <= n_feet <= 2^20.
+ * dirs and weights are read once per call for all feet.  ws: find_skin_fwd_ws_bytes / find_skin_bwd_ws_bytes (-1 for bad sizes).
+ * find_skin_bwd: d_out (n_feet, V, 3) -> d_pose, d_betas, d_trans (shaped as their inputs); the model gets no gradient.  Sums over the
+ * vertices go tile by tile in a fixed order: no atomics, bit-identical from run to run, and a foot's rows do not depend on n_feet.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t find_skin_fwd_ws_bytes(int64_t n_feet, int64_t V, int64_t J, int64_t B, int64_t P);
+int find_skin_fwd(const float* v_template, const float* dirs, const float* J0, const float* JS, const float* weights, const int32_t* parent, int64_t V,
+				  int64_t J, int64_t B, int64_t P, const float* pose, const float* betas, const float* trans, int64_t n_feet, float* out, float* joints,
+				  void* ws, int64_t ws_bytes, void* stream);
+int64_t find_skin_bwd_ws_bytes(int64_t n_feet, int64_t V, int64_t J, int64_t B, int64_t P);
+int find_skin_bwd(const float* v_template, const float* dirs, const float* J0, const float* JS, const float* weights, const int32_t* parent, int64_t V,
+				  int64_t J, int64_t B, int64_t P, const float* pose, const float* betas, const float* d_out, int64_t n_feet, float* d_pose,
+				  float* d_betas, float* d_trans, void* ws, int64_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Surface sampling gather.  Replaces the gather/lerp half of pytorch3d.ops.sample_points_from_meshes
  * (call sites src/model/losses.py:39-41,63,67; src/eval/eval_3d.py:149-150); the random draws
  * (face index, u, v) are INPUTS so CPU and GPU runs see identical samples.
