@@ -102,6 +102,9 @@ PROTOTYPES = {
 	'find_plane_sections_bwd': (c_int, [_P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P]),
 	'find_extents_fwd': (c_int, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
 	'find_extents_bwd': (c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P]),
+	'find_section_hull_ws_bytes': (c_int64, [_I, _I, _I, _I, c_int]),
+	'find_section_hull_fwd': (c_int, [_P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
+	'find_section_hull_bwd': (c_int, [_P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P]),
 	'find_align_ws_bytes': (c_int64, [_I, _I]),
 	'find_align_fit': (c_int, [_P, _P, _P, _P, _I, _I, c_int, c_int, _P, _P, _P, _P, _P, _I, _P]),
 	'find_icp_ws_bytes': (c_int64, [_I, _I, _I]),

@@ -162,12 +162,15 @@ class FootSpec:
 	y across the foot), normalised here.  Length and width are the extents of the vertices along them.  girths: (name, fraction) pairs; a girth
 	is the perimeter of the section by the plane normal to the length axis at that fraction of the foot's OWN length from the heel,
 	d = lo + fraction * (hi - lo) along the length axis.  The defaults -- ball at 0.68, instep at 0.50 of the length -- are this project's
-	convention, not a standard: they are configurable.  Not claimed: the ISO ball-girth plane through the two metatarsal heads (a tilted
-	plane from landmarks), or a tape's girth, which is the perimeter of the section's convex hull -- a section perimeter is at least the
-	tape's number, and larger wherever the sole is concave."""
+	convention, not a standard: they are configurable.  girth_kind: 'section' (the default) measures that perimeter, plane_sections';
+	'tape' measures the perimeter of the section's convex hull, girth.section_hulls' -- what a tape reads: a section perimeter is at least the
+	tape's number, and larger wherever the sole is concave or the plane cuts the toes into separate loops.  Not claimed by either: the ISO
+	ball-girth plane through the two metatarsal heads (a tilted plane from landmarks); girth.plane_through builds that plane for a caller
+	who knows the landmark vertices."""
 	length_axis: tuple = (1., 0., 0.)
 	width_axis: tuple = (0., 1., 0.)
 	girths: tuple = (('ball', 0.68), ('instep', 0.50))
+	girth_kind: str = 'section'
 
 	def __post_init__(self):
 		object.__setattr__(self, 'length_axis', _unit(self.length_axis, 'length_axis'))
@@ -176,6 +179,8 @@ class FootSpec:
 		if len(girths) > MAX_PLANES or not all(0. <= f <= 1. for _, f in girths) or len({n for n, _ in girths}) != len(girths):
 			raise ValueError(f'FootSpec: at most {MAX_PLANES} girths (name, fraction in [0, 1]) of distinct names, got {self.girths!r}')
 		object.__setattr__(self, 'girths', girths)
+		if self.girth_kind not in ('section', 'tape'):
+			raise ValueError(f"FootSpec: girth_kind must be 'section' or 'tape', got {self.girth_kind!r}")
 
 	@property
 	def names(self):
@@ -192,7 +197,8 @@ def _spec_tensors(spec, device):
 def foot_measurements(verts, faces, spec=FootSpec(), v_len=None):
 	"""(values (N, M) fp32 in metres, names): with the default spec ('length', 'width', 'ball_girth', 'instep_girth').  verts (N, V, 3) registered
 	vertices, faces (F, 3) or (N, F, 3) (-1 padded), v_len (N) the vertex counts of a padded batch.  One extents call and one plane_sections
-	call; the gradient reaches the vertices directly and, for the girths, through the offsets of their planes (the heel and toe vertices)."""
+	call (girth_kind 'tape': one girth.section_hulls call); the gradient reaches the vertices directly and, for the girths, through the offsets
+	of their planes (the heel and toe vertices)."""
 	if not isinstance(spec, FootSpec):
 		raise ValueError(f'find_amd.measure.foot_measurements: spec must be a FootSpec, got {type(spec).__name__}')
 	dirs, frac = _spec_tensors(spec, verts.device)
@@ -202,7 +208,12 @@ def foot_measurements(verts, faces, spec=FootSpec(), v_len=None):
 	if spec.girths:
 		N, G = verts.shape[0], len(spec.girths)
 		d = lo[:, :1] + frac[None] * size[:, :1]
-		cols.append(plane_sections(verts, faces, torch.cat([dirs[0].expand(N, G, 3), d[..., None]], dim=-1)))
+		planes = torch.cat([dirs[0].expand(N, G, 3), d[..., None]], dim=-1)
+		if spec.girth_kind == 'tape':
+			from .girth import section_hulls   # (a module of its own: it allocates)
+			cols.append(section_hulls(verts, faces, planes))
+		else:
+			cols.append(plane_sections(verts, faces, planes))
 	return torch.cat(cols, dim=1), spec.names
 
 

@@ -790,6 +790,37 @@ int find_extents_bwd(const float* g_lo, const float* g_hi, const int32_t* arg_lo
 					 int64_t V, int64_t D, float* d_verts, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Tape girths (girth.hip): the perimeter of the convex hull of a plane section.  Not in the reference.  verts, faces, planes as above; the
+ * points of (mesh, plane) are the crossing points of the section rule above, two per crossing face: edge 0 joins the face's lone vertex L
+ * (corner k) to corner k + 1, edge 1 to corner k + 2; id = 2 face + edge.  The two faces of a mesh edge give the same bits.
+ *   The hull is taken in the plane's 2-D coordinates (x, y) = (p . e1, p . e2), each fmaf(e_z, p_z, fmaf(e_y, p_y, e_x * p_x)) in fp32, with
+ *   a the coordinate axis of the smallest |n_k| (lowest index on ties), e1 = normalize(n x a), e2 = n x e1.  Corners are strict: points
+ *   identical in (x, y) count once, owned by the smallest id; of points collinear with a hull edge only its end points are corners.  The
+ *   orientation predicate is evaluated in double on the fp32 coordinates.  The corners run counter-clockwise (seen against e1 x e2 = n) from
+ *   the point of the smallest (x, y, id).
+ * find_section_hull_fwd: girth (N, P) fp32 the sum of the 3-D distances |p_i - p_i+1| around the loop, each fp32, summed in double in a
+ *   fixed order; two distinct points give 2 |p1 - p2|, one or none 0.  count (N, P) int32 the crossing faces (as find_plane_sections_fwd),
+ *   n_hull (N, P) int32 the corners, status (N, P) int32: bit 1 more than max_points crossing faces, bit 2 the walk did not close within
+ *   one step per point; a status != 0 gives girth 0 and n_hull 0.  hull_ids (N, P, 2 max_points) int32: the first n_hull entries are the
+ *   corners' ids in order, the rest is not written.  hull_points (N, P, max_hull, 3) or NULL (max_hull 0): the corners' points in order,
+ *   zeros past n_hull, truncated at max_hull (<= 2 max_points).  One workgroup per (mesh, plane) compacts its crossing faces in face order and
+ *   walks the hull, on chip up to 2048 points and from the workspace beyond.  No atomics: bit-identical on repeat, and a mesh's row does not
+ *   depend on the rest of the batch.  ws: find_section_hull_ws_bytes(N, F, P, max_points, 0) bytes, 8-byte aligned.
+ * find_section_hull_bwd: from g (N, P), n_hull and hull_ids: d_verts (N, V, 3) OVERWRITTEN, every element; d_planes (planes_batch, P, 4) or
+ *   NULL, all four components (ds / dn = v, ds / dd = -1; the normal is not renormalised), for planes_batch 1 summed over the meshes in
+ *   mesh order.  A corner p between a and b receives g ((p - a) / |p - a| + (p - b) / |p - b|), a zero distance masked; the sums into a
+ *   vertex run in plane order, then corner order.  ws: find_section_hull_ws_bytes(N, F, P, max_points, 1) bytes.
+ * find_section_hull_ws_bytes: -1 for bad sizes (as find_plane_sections_ws_bytes, and max_points outside 1 .. F).
+ * ---------------------------------------------------------------------------------------------- */
+int64_t find_section_hull_ws_bytes(int64_t N, int64_t F, int64_t P, int64_t max_points, int backward);
+int find_section_hull_fwd(const float* verts, const int32_t* faces, int64_t faces_batch, const float* planes, int64_t planes_batch, int64_t N,
+						  int64_t V, int64_t F, int64_t P, int64_t max_points, int64_t max_hull, float* girth, int32_t* count, int32_t* n_hull,
+						  int32_t* status, int32_t* hull_ids, float* hull_points, void* ws, int64_t ws_bytes, void* stream);
+int find_section_hull_bwd(const float* verts, const int32_t* faces, int64_t faces_batch, const float* planes, int64_t planes_batch, int64_t N,
+						  int64_t V, int64_t F, int64_t P, int64_t max_points, const float* g, const int32_t* n_hull, const int32_t* hull_ids,
+						  float* d_verts, float* d_planes, void* ws, int64_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Rigid and similarity alignment of point clouds (align.hip).  Not in the reference; stands in for
  * pytorch3d.ops.corresponding_points_alignment and iterative_closest_point.  Row vectors: x' = s (x @ R) + t, R (n, 3, 3) row-major.
  * No allocation, no host synchronisation and no float atomics in either call; every sum is taken in double in a fixed order (256 pairs per
