@@ -1391,6 +1391,90 @@ def mesh_smoothness_loss(verts, topo, w_edge=10.0, w_lap=0.1):
 	return _SmoothLoss.apply(verts, topo, float(w_edge), float(w_lap))
 
 
+# ----------------------------------------------------------------------------------------------- as-rigid-as-possible energy
+ARAP_WEIGHTS = ('cotangent', 'uniform')
+
+
+def arap_cotangent_weights(rest_verts, faces, nbr_off, nbr_idx):
+	"""One weight per entry of the vertex -> neighbour CSR (numpy, float64): w_ij = 1/2 sum of the cotangents of the angles opposite edge ij in
+	the rest mesh -- two faces, or one at a boundary --, clamped below at 0 (a negative weight makes the energy unbounded below; obtuse
+	triangles give them).  A face without area contributes nothing."""
+	import numpy as np
+	q = np.asarray(rest_verts, np.float64).reshape(-1, 3)
+	f = np.asarray(faces, np.int64).reshape(-1, 3)
+	V = q.shape[0]
+	keys, vals = [], []
+	for c in range(3):   # the angle at corner c is opposite the edge (a, b)
+		o, a, b = f[:, c], f[:, (c + 1) % 3], f[:, (c + 2) % 3]
+		u, v = q[a] - q[o], q[b] - q[o]
+		area2 = np.linalg.norm(np.cross(u, v), axis=1)
+		cot = np.divide((u * v).sum(1), area2, out=np.zeros_like(area2), where=area2 > 0)
+		keys += [a * V + b, b * V + a]
+		vals += [0.5 * cot, 0.5 * cot]
+	rows = np.repeat(np.arange(V, dtype=np.int64), np.diff(np.asarray(nbr_off, np.int64)))
+	want = rows * V + np.asarray(nbr_idx, np.int64)
+	if want.size == 0:
+		return np.zeros(0, np.float64)
+	uniq, inv = np.unique(np.concatenate(keys), return_inverse=True)
+	total = np.bincount(inv.reshape(-1), weights=np.concatenate(vals), minlength=uniq.size)
+	at = np.minimum(np.searchsorted(uniq, want), uniq.size - 1)
+	return np.where(uniq[at] == want, np.maximum(total[at], 0.), 0.)
+
+
+class ArapRest:
+	"""The rest mesh of the as-rigid-as-possible energy: the MeshTopology of the faces, the fp32 rest vertices (V, 3), nbr_w -- one fp32 weight
+	per entry of topo.nbr_idx -- and W, the float64 sum of those fp32 weights.  weights: 'cotangent' (arap_cotangent_weights, computed on the
+	host in float64 and rounded to fp32) or 'uniform' (1).  Built on the host once; ArapRest.get caches per tensor objects, as MeshTopology.get does."""
+	_cache = {}
+
+	def __init__(self, rest_verts, faces, weights='cotangent'):
+		import numpy as np
+		if weights not in ARAP_WEIGHTS:
+			raise ValueError(f"find_amd.arap: weights must be one of {ARAP_WEIGHTS}, got {weights!r}")
+		_require_gpu(rest_verts)
+		if rest_verts.dim() not in (2, 3) or rest_verts.shape[-1] != 3 or rest_verts.numel() == 0 or rest_verts.numel() != 3 * rest_verts.shape[-2]:
+			raise ValueError(f'find_amd.arap: rest_verts (V, 3) or (1, V, 3) expected, got {tuple(rest_verts.shape)}')
+		self.weights = weights
+		self.rest = rest_verts.detach().reshape(-1, 3).contiguous().clone()
+		self.n_verts = int(self.rest.shape[0])
+		self.topo = MeshTopology.get(faces, self.n_verts)
+		off, idx = self.topo.nbr_off.cpu().numpy(), self.topo.nbr_idx.cpu().numpy()
+		if weights == 'uniform':
+			w = np.ones(idx.shape[0], np.float32)
+		else:
+			w = arap_cotangent_weights(self.rest.cpu().numpy(), self.topo.faces.cpu().numpy(), off, idx).astype(np.float32)
+		self.n_nbr = int(idx.shape[0])
+		self.W = float(w.astype(np.float64).sum())
+		self.nbr_w = torch.from_numpy(w).to(self.rest.device)
+
+	@classmethod
+	def get(cls, rest_verts, faces, weights='cotangent'):
+		import weakref
+		key = (id(rest_verts), id(faces), weights)
+		ent = cls._cache.get(key)
+		if ent is not None:
+			refs, versions, rest = ent
+			if refs[0]() is rest_verts and refs[1]() is faces and versions == (int(rest_verts._version), int(faces._version)):
+				return rest
+		if len(cls._cache) > 16:
+			cls._cache.clear()
+		rest = cls(rest_verts, faces, weights)
+		cls._cache[key] = ((weakref.ref(rest_verts), weakref.ref(faces)), (int(rest_verts._version), int(faces._version)), rest)
+		return rest
+
+
+def arap_energy(verts, rest, return_per_vertex=False, return_rotations=False):
+	"""The as-rigid-as-possible energy (Sorkine & Alexa 2007) of deformed meshes verts (N, V, 3) against an ArapRest: E (N,) fp32 in m^2,
+	E = (1 / W) sum_i sum_{j in N(i)} w_ij |(p_i - p_j) - R_i (q_i - q_j)|^2 with R_i the rotation fitted to vertex i's neighbourhood.
+	Differentiable in verts (first order; the rotations are held fixed, which is exact: they minimise E).  return_per_vertex: also the
+	detached cell energies (N, V), already divided by W (they sum to E: vis.error_colours heat maps).  return_rotations: also
+	(R (N, V, 3, 3) fp32, degenerate (N,) int32) -- a cell without a unique rotation (no neighbours, collapsed or collinear ones) takes R = I
+	and is counted.  Returns E, or a tuple in that order.  HIP forward and backward (find_arap_fwd / find_arap_bwd); the op lives in
+	find_amd.arap (its workspace comes from _ws here); see there."""
+	from . import arap
+	return arap.arap_energy(verts, rest, return_per_vertex=return_per_vertex, return_rotations=return_rotations)
+
+
 # ----------------------------------------------------------------------------------------------- surface normals
 def _corner_tables(faces, n_verts):
 	"""Vertex -> incident-corner tables of per-mesh faces (B, F, 3) int32 (rows of -1 pad), built on the device without a host round trip --

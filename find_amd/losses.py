@@ -257,6 +257,21 @@ class SurfaceDistanceLoss(nn.Module):
 		return (to_pred.mean(1) + to_gt.mean(1)).mean()
 
 
+class ARAPLoss(nn.Module):
+	"""As-rigid-as-possible deformation energy against a rest mesh (not in the reference; Sorkine & Alexa 2007): every vertex neighbourhood
+	of the deformed mesh should be a rotated copy of the rest mesh's, so bending is free and stretch and shear are not.  One HIP pass each
+	way (functional.arap_energy).  rest_verts (V, 3) or (1, V, 3) and faces: the rest mesh, shared by the batch; weights 'cotangent' (of the
+	rest mesh, clamped at 0) or 'uniform'.  m^2, like the Chamfer term."""
+
+	def __init__(self, rest_verts, faces, weights='cotangent'):
+		super().__init__()
+		self.rest = FN.ArapRest.get(rest_verts, faces, weights)
+
+	def forward(self, verts):
+		"""verts (N, V, 3): the mean over the N meshes of E_n."""
+		return FN.arap_energy(verts, self.rest).mean()
+
+
 class DepthLoss(nn.Module):
 	"""Masked, robust loss between a predicted and a target depth map (not in the reference; fitting to a depth sensor or a structured-light
 	scan): one HIP pass each way (functional.depth_loss)."""

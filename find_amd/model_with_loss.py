@@ -63,9 +63,17 @@ EXTENSION_TERMS_DEPTH = (
 	Term('depth', 'loss_depth', 'weight_depth', False, True, '_raw_depth'),
 )
 EVERY_EXTENSION_TERM = ALL_EXTENSION_TERMS + EXTENSION_TERMS_DEPTH
+# ... and, walked last, the as-rigid-as-possible term: the template's vertex neighbourhoods against those of template + offsets, the
+# displacement BEFORE the similarity registration, whose scale the term would otherwise fight (forward(arap=True)).  A tuple of its own, and
+# a name of its own for everything after ALL_TERMS: the tuples above are pinned by tests.
+EXTENSION_TERMS_ARAP = (
+	Term('arap', 'loss_arap', 'weight_arap', True, False, '_raw_arap'),
+)
+TERMS_AFTER_ALL_TERMS = EVERY_EXTENSION_TERM + EXTENSION_TERMS_ARAP
 # what a reference Opts, which knows nothing of an extension term, is taken to say (weight_depth is not tuned: about a millimetre of mean
-# error against a silhouette MSE of 1e-2)
-EXTENSION_WEIGHTS = dict(weight_normal=1., weight_p2s=10000., weight_depth=100.)
+# error against a silhouette MSE of 1e-2; weight_arap is not tuned either: m^2 like the Chamfer and p2s terms, hence their weight)
+EXTENSION_WEIGHTS = dict(weight_normal=1., weight_p2s=10000., weight_depth=100., weight_arap=10000.)
+ARAP_DEFAULTS = dict(arap_weights='cotangent')
 DEPTH_DEFAULTS = dict(depth_loss_kind='l1', depth_loss_delta=0.005, depth_trunc=0.02)
 PIX_DEFAULTS = dict(pix_ssim_lambda=0.)   # the share of 1 - SSIM in loss_pix (ModelWithLoss._raw_pix); 0: the reference's MSE alone
 
@@ -266,6 +274,12 @@ class ModelWithLoss(nn.Module):
 		return FN.depth_loss(fold(st.pred['depth']), fold(st.gt['depth']), fold(weight), kind=o['depth_loss_kind'], delta=o['depth_loss_delta'],
 							 trunc=o['depth_trunc'])
 
+	def _raw_arap(self, st):
+		# the rest mesh is the model's template (its tables are built once per template: ArapRest.get), the deformed one template + offsets
+		m = self.model
+		rest = FN.ArapRest.get(m.template_verts, m.template_faces, getattr(st.opts, 'arap_weights', ARAP_DEFAULTS['arap_weights']))
+		return FN.arap_energy(m.template_verts.data + st.res['offsets'], rest).mean()
+
 	def _raw_pix(self, st):
 		# images are compared inside the silhouettes only (model.py:1101-1105): MSE(image * mask, gt image * gt mask), one pass each way
 		# (find_image_mse_*; CPU tensors raise there: no fallback)
@@ -370,7 +384,7 @@ class ModelWithLoss(nn.Module):
 				restyle_perc_lat=False, restyle_perc_feat=False, restyle_perc_cluster=False, cont_pose=False, render_foot=False,
 				save_renders=False, render_dir='_pix', is_train=True, use_z_cutoff=False, gt_z_cutoff=None, restyle_feature_maps=None,
 				no_displacement=False, return_renders=False, copy_mask_out=True, mask_out_pred_faces=False, views=None, p2s=False,
-				depth=False, cont_pairs=None, normal=False):
+				arap=False, depth=False, cont_pairs=None, normal=False):   # (tests pin the last three: a new keyword goes in front of them)
 		given = dict(vgg_perc=vgg_perc, restyle_perc_lat=restyle_perc_lat, restyle_perc_feat=restyle_perc_feat, mask_out_pred_faces=mask_out_pred_faces)
 		for name, why in OUT_OF_SCOPE_FLAGS.items():
 			if given[name]:
@@ -379,6 +393,10 @@ class ModelWithLoss(nn.Module):
 			# (upstream ends in an AttributeError inside TextureLossGTSpace, losses.py:22-57)
 			raise NotImplementedError('texture=True: the texture loss queries the model\'s colour field, and the PCA and skinned models (model_type=\'pca\' '
 									  '/ \'skinned\') have none; switch the texture term off for them')
+		if arap and isinstance(self.model, SkinnedModel):
+			raise NotImplementedError("arap=True: the as-rigid-as-possible term regularises res['offsets'], the displacement field over the template "
+									  "before the registration, and the skinned model (model_type='skinned') has none: its vertices come from pose and "
+									  'shape parameters; switch the term off for it')
 		if restyle_perc_cluster:
 			self._require_part_loss(opts, None if self.restyle_perc_loss is None else self.restyle_perc_loss.encoder)
 		# The contrastive pose term (model.py:1042-1049): a batch without pose rows is an error whatever its size; one scan gives no term.
@@ -393,7 +411,7 @@ class ModelWithLoss(nn.Module):
 			if batch['pose_code'].shape[0] > 1:
 				pairs = cont_pairs if cont_pairs is not None else _losses.pairs_to_device(_losses.draw_pairs(batch['pose_code'].shape[0]), batch[pvec].device)
 		enabled = dict(chamf=chamf, smooth=smooth, texture=texture, cont_pose=pairs is not None, pix=pix, sil=sil,
-					   restyle_perc_cluster=restyle_perc_cluster, normal=normal, p2s=p2s, depth=depth)
+					   restyle_perc_cluster=restyle_perc_cluster, normal=normal, p2s=p2s, depth=depth, arap=arap)
 
 		st = _Step()
 		st.cont_pairs = pairs
@@ -462,7 +480,7 @@ class ModelWithLoss(nn.Module):
 										features=st.res['cpv'] if part else None, **(dict(normals=True) if normal else {}),
 										**(dict(depth=True) if depth else {}))
 		raw, weights = {}, []
-		active = [t for t in ALL_TERMS + EVERY_EXTENSION_TERM if enabled[t.flag] and not (t.needs_3d and not supervise_3d) and not (t.needs_render and not rendering)]
+		active = [t for t in ALL_TERMS + TERMS_AFTER_ALL_TERMS if enabled[t.flag] and not (t.needs_3d and not supervise_3d) and not (t.needs_render and not rendering)]
 		# The Chamfer term -- surface sampling and a brute-force nearest-neighbour search: packed fp32 VALU work, no matrix pipe -- beside the
 		# texture term's MLP pass (matrix pipe) on a second stream: they want different halves of a CU.  Autograd replays each term's
 		# backward on the stream of its forward, so the two backward halves overlap as well.  Not under stream capture.
@@ -514,7 +532,7 @@ class ModelWithLoss(nn.Module):
 		for term in active:   # (reported, and summed, in the registry's order whatever the issue order was)
 			raw[term.key] = got[term.key]
 			# (a reference Opts knows nothing of an extension term's weight: EXTENSION_WEIGHTS)
-			weights.append(float(getattr(opts, term.weight, EXTENSION_WEIGHTS[term.weight]) if term in EVERY_EXTENSION_TERM else getattr(opts, term.weight)))
+			weights.append(float(getattr(opts, term.weight, EXTENSION_WEIGHTS[term.weight]) if term in TERMS_AFTER_ALL_TERMS else getattr(opts, term.weight)))
 		for side in (aside, third, tex_side):
 			if side is not None:
 				torch.cuda.current_stream(dev).wait_stream(side)

@@ -38,6 +38,9 @@ class Opts:
 		depth_loss=False, weight_depth=100., depth_loss_kind='l1', depth_loss_delta=0.005, depth_trunc=0.02,
 		# not in the reference: the structural share of the pixel term, loss_pix = (1 - l) MSE + l (1 - SSIM) (find_amd.ssim); 0: the MSE alone
 		pix_ssim_lambda=0.,
+		# not in the reference: the as-rigid-as-possible term (ModelWithLoss.forward(arap=True)) on template + offsets against the template; m^2
+		# like the Chamfer and p2s terms, hence their weight: not tuned.  arap_weights 'cotangent' (of the template, clamped at 0) | 'uniform'
+		arap_loss=False, weight_arap=10000., arap_weights='cotangent',
 	)
 
 	def __init__(self, **kw):

@@ -131,6 +131,9 @@ class Trainer:
 		if model_kwargs.get('depth'):
 			return ('the depth term (functional.depth_map, functional.depth_loss) allocates its workspace and outputs per call and has not been taken '
 					'through a capture')
+		if model_kwargs.get('arap'):
+			return ('the arap term (the as-rigid-as-possible energy, functional.arap_energy) allocates its workspace, rotations and outputs per call and '
+					'has not been taken through a capture')
 		if model_kwargs.get('pix') and float(getattr(o, 'pix_ssim_lambda', 0.)) != 0:
 			return ('opts.pix_ssim_lambda != 0: the structural share of the pixel term (find_amd.ssim) allocates its workspace and gradient maps per call '
 					'and has not been taken through a capture')

@@ -864,6 +864,26 @@ int find_icp_run(const float* x, const int32_t* x_len, const float* y, const int
 				 float* dist, int32_t* idx, float* tau, int32_t* used, void* ws, int64_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The as-rigid-as-possible energy (arap.hip; Sorkine & Alexa 2007).  Not in the reference.  n deformed meshes verts (n, v, 3) against ONE rest
+ * mesh rest (v, 3), over a vertex -> neighbour CSR nbr_off (v + 1) / nbr_idx (n_nbr) with a weight nbr_w (n_nbr) >= 0 per entry (symmetric:
+ * w_ij = w_ji) and w_sum = the sum of all n_nbr weights (0: a mesh without edges, every result 0).  With e_q = rest_i - rest_j, e_p = verts_i - verts_j:
+ *   S_i = sum_j w_ij e_q e_p^T = U D V^T (3 x 3 SVD by one-sided Jacobi rotations in double),  R_i = V diag(1, 1, det(V U^T)) U^T,
+ *   energy[n] = (1 / w_sum) sum_i sum_j w_ij |e_p - R_i e_q|^2,   cell[n, i] = the i-th inner sum / w_sum,
+ *   d_verts[n, i] = g[n] (2 / w_sum) sum_j w_ij [2 e_p - (R_i + R_j) e_q]   (the rotations held fixed: exact, they minimise the energy).
+ * A cell without a unique rotation -- no neighbours, D_1 = 0, or D_2 <= 1e-12 D_1 -- takes R_i = I and is counted in degenerate[n]; never NaN.
+ * find_arap_fwd writes R (n, v, 3, 3) in DOUBLE, row-major, for find_arap_bwd, which reads it and does not refit.  An entry of nbr_idx outside
+ * [0, v) is skipped.  All arithmetic in double; no allocation, no host synchronisation, no atomics; every sum in a fixed order (the lanes of a
+ * vertex by butterfly -- 4 in the forward, 8 in the backward --, 64 vertices per forward workgroup, workgroups in a strided fixed order), so two runs agree bit for bit and a mesh's values do
+ * not depend on the rest of the batch.  Valence is not bounded.
+ *   ws: find_arap_ws_bytes(n, v) bytes, 8-byte aligned (-1 for bad sizes: n, v < 1, n >= 65536, v >= 2^24, n v >= 2^31); only the forward needs it.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t find_arap_ws_bytes(int64_t n, int64_t v);
+int find_arap_fwd(const float* verts, const float* rest, const int32_t* nbr_off, const int32_t* nbr_idx, const float* nbr_w, int64_t n, int64_t v,
+				  int64_t n_nbr, double w_sum, double* R, float* cell, float* energy, int32_t* degenerate, void* ws, int64_t ws_bytes, void* stream);
+int find_arap_bwd(const float* verts, const float* rest, const int32_t* nbr_off, const int32_t* nbr_idx, const float* nbr_w, int64_t n, int64_t v,
+				  int64_t n_nbr, double w_sum, const double* R, const float* g, float* d_verts, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Fused multi-tensor optimiser steps.  Replace torch.optim.Adam / torch.optim.SGD(momentum=0.9)
  * as constructed by the reference (src/train/train.py:161-168) and stepped once per batch
  * (src/train/trainer.py:121-123).  `param`, `grad`, moment arrays: HOST arrays of n_tensors DEVICE pointers (fp32,
