@@ -12,9 +12,10 @@ import torch
 
 from . import align as _align
 from . import functional as FN
+from . import inside as _inside
 from . import measure as _measure
 from . import ssim as _ssim
-from .losses import point_mesh_distance, sample_points_from_meshes
+from .losses import _mesh_faces, point_mesh_distance, sample_points_from_meshes
 
 # template vertex ids of the six keypoints on the PCA foot model's mesh (reference src/cfg.yaml:11, read by eval_3d.py:137-138 and
 # eval_2d.py:155-156): eval_3d_metrics(..., template_kp_idxs=PCA_KEYPOINTS) for a PCAModel fitted to Foot3D scans
@@ -54,8 +55,16 @@ def measurement_errors_mm(pred_meshes, gt_meshes, spec=None, return_per_foot=Fal
 	return (out, pred, gt) if return_per_foot else out
 
 
+def _mesh_boxes(meshes):
+	"""(lo (N, 3), hi (N, 3)) over each mesh's own vertices (the rows that pad a ragged batch do not count)."""
+	v = meshes.verts_padded()
+	own = (torch.arange(v.shape[1], device=v.device)[None] < meshes.num_verts_per_mesh().to(v.device)[:, None])[..., None]
+	inf = torch.full_like(v, float('inf'))
+	return torch.where(own, v, inf).amin(1), torch.where(own, v, -inf).amax(1)
+
+
 def eval_3d_metrics(pred_meshes, gt_meshes, pred_verts=None, template_kp_idxs=None, gt_kps=None, samples=10000, z_cutoff=0.07,
-					draws_gt=None, draws_pred=None, return_samples=False, surface=False, return_per_foot=False, align=None, measurements=None):
+					draws_gt=None, draws_pred=None, return_samples=False, surface=False, return_per_foot=False, align=None, volume=None, measurements=None):
 	"""Returns {'Keypoint (mm)', 'Chamf z-cutoff <z> (um)', 'Chamf (um)'} as 0-d tensors (keypoints only when given); with return_samples
 	also (gt_pts, pred_pts), the (N,samples,3) surface samples the Chamfer terms were taken on (the per-vertex heat maps of eval_3d.py:171-178
 	read the predicted ones: no second draw).
@@ -70,7 +79,14 @@ def eval_3d_metrics(pred_meshes, gt_meshes, pred_verts=None, template_kp_idxs=No
 	(or a similarity).  The prediction is moved onto the scan by find_amd.align.iterative_closest_point from the very predicted samples to
 	the very scan samples the Chamfer term drew -- no further random number is drawn -- and 'Chamf aligned (μm)' is the Chamfer term of the
 	moved samples; with keypoints 'Keypoint aligned (mm)' is the keypoint error of the predicted keypoints under the same transform.  With
-	return_per_foot the last value also holds 'align_R' (N, 3, 3), 'align_T' (N, 3), 'align_s' (N) and 'align_rmse' (N).  None changes nothing."""
+	return_per_foot the last value also holds 'align_R' (N, 3, 3), 'align_T' (N, 3), 'align_s' (N) and 'align_rmse' (N).  None changes nothing.
+	volume (not in the reference; None or a grid resolution): find_amd.inside.volume_iou of every prediction with its scan on one volume^3 grid
+	over the two (5 mm of margin): 'Vol IoU (%)', the mean over feet of the volumetric IoU x 100, and 'Volume err (ml)', the mean of
+	|V_pred - V_scan| x 1e6 of the two grid volumes (winding number > 0.5 at the cell centres, so a scan open at the ankle is closed about flat).
+	With return_per_foot the last value also holds 'vol_iou', 'volume_pred_ml' and 'volume_gt_ml' (N).  No random number is drawn for them;
+	None changes nothing."""
+	if volume is not None and (not isinstance(volume, int) or isinstance(volume, bool) or volume < 1):
+		raise ValueError(f'find_amd.eval_metrics.eval_3d_metrics: volume must be None or a grid resolution (an int >= 1), got {volume!r}')
 	if align not in (None, 'rigid', 'similarity'):
 		raise ValueError(f"find_amd.eval_metrics.eval_3d_metrics: align must be None, 'rigid' or 'similarity', got {align!r}")
 	spec = None if measurements is None or measurements is False else _foot_spec(measurements, 'eval_metrics.eval_3d_metrics')
@@ -105,6 +121,14 @@ def eval_3d_metrics(pred_meshes, gt_meshes, pred_verts=None, template_kp_idxs=No
 		if spec is not None:
 			errs, per_foot['measure_pred_mm'], per_foot['measure_gt_mm'] = measurement_errors_mm(pred_meshes, gt_meshes, spec, return_per_foot=True)
 			out.update(errs)
+		if volume is not None:
+			lo_p, hi_p = _mesh_boxes(pred_meshes)
+			lo_g, hi_g = _mesh_boxes(gt_meshes)
+			iou, vol_p, vol_g = _inside.volume_iou(pred_meshes.verts_padded(), _mesh_faces(pred_meshes), gt_meshes.verts_padded(), _mesh_faces(gt_meshes), res=volume,
+												   bounds=(torch.minimum(lo_p, lo_g) - 0.005, torch.maximum(hi_p, hi_g) + 0.005))
+			per_foot.update(vol_iou=iou, volume_pred_ml=vol_p * 1e6, volume_gt_ml=vol_g * 1e6)
+			out['Vol IoU (%)'] = iou.mean() * 100
+			out['Volume err (ml)'] = (vol_p - vol_g).abs().mean() * 1e6
 		if align is not None:
 			sol = _align.iterative_closest_point(pred_pts, gt_pts, estimate_scale=align == 'similarity')
 			out['Chamf aligned (μm)'] = FN.chamfer_distance(gt_pts, sol.Xt)[0] * 1e6
@@ -112,7 +136,7 @@ def eval_3d_metrics(pred_meshes, gt_meshes, pred_verts=None, template_kp_idxs=No
 				kp = torch.as_tensor(template_kp_idxs, device=pred_verts.device, dtype=torch.long)
 				out['Keypoint aligned (mm)'] = torch.norm(sol.RTs.apply(pred_verts[:, kp]) - gt_kps, dim=-1).mean() * 1e3
 			per_foot.update(align_R=sol.RTs.R, align_T=sol.RTs.T, align_s=sol.RTs.s, align_rmse=sol.rmse)
-	ret = (out,) + (((gt_pts, pred_pts),) if return_samples else ()) + ((per_foot,) if (surface or spec is not None or align is not None) and return_per_foot else ())
+	ret = (out,) + (((gt_pts, pred_pts),) if return_samples else ()) + ((per_foot,) if (surface or spec is not None or align is not None or volume is not None) and return_per_foot else ())
 	return ret if len(ret) > 1 else out
 
 

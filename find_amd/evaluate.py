@@ -98,7 +98,7 @@ def _ssim_columns(pred_rdrs, gt_rdrs, batch_size):
 
 def eval_3d(model, dataset, template_kp_idxs, samples=10000, z_cutoff=0.07, feet_per_call=16, render_correspondences=False, image_size=256,
 			return_per_foot=False, device='cuda', produce_spins=False, export_meshes=False, out_dir=None, spin_frames=250, spin_image_size=512,
-			spin_format='gif', surface=False, template_uvs=None, texture_size=1024, texture_pad=4, align=None, measurements=False):
+			spin_format='gif', surface=False, template_uvs=None, texture_size=1024, texture_pad=4, align=None, volume=None, measurements=False):
 	"""model: a NeuralDisplacementField, a PCAModel or a SkinnedModel -- any model with latent_vectors_val and get_meshes_from_batch -- whose
 	validation latent tables are indexed by the dataset's item index (batch['idx']);
 	dataset: the validation Foot3DDataset, every foot with keypoints; template_kp_idxs: the template vertices of the keypoints (the
@@ -129,7 +129,10 @@ def eval_3d(model, dataset, template_kp_idxs, samples=10000, z_cutoff=0.07, feet
 	|prediction - scan|; with return_per_foot the second dict also holds 'measure_pred_mm' and 'measure_gt_mm' (N, M).  False: nothing changes.
 	align (not in the reference; None, 'rigid' or 'similarity'): eval_metrics.eval_3d_metrics(align=...) -- 'Chamf aligned (μm)' and 'Keypoint
 	aligned (mm)', the errors after the prediction has been moved onto the scan by ICP on the Chamfer term's own samples, join the returned
-	metrics; with return_per_foot the second dict also holds 'align_R', 'align_T', 'align_s' and 'align_rmse'.  None: nothing changes."""
+	metrics; with return_per_foot the second dict also holds 'align_R', 'align_T', 'align_s' and 'align_rmse'.  None: nothing changes.
+	volume (not in the reference; None or a grid resolution): eval_metrics.eval_3d_metrics(volume=...) -- 'Vol IoU (%)' and 'Volume err (ml)',
+	the volumetric IoU and the volume difference of prediction and scan on a volume^3 grid (find_amd.inside), join the returned metrics; with
+	return_per_foot the second dict also holds 'vol_iou', 'volume_pred_ml' and 'volume_gt_ml' (N).  None: nothing changes."""
 	if align not in (None, 'rigid', 'similarity'):
 		raise ValueError(f"find_amd.evaluate.eval_3d: align must be None, 'rigid' or 'similarity', got {align!r}")
 	spec = _foot_spec(measurements, 'evaluate.eval_3d') if measurements is not False and measurements is not None else None
@@ -182,10 +185,10 @@ def eval_3d(model, dataset, template_kp_idxs, samples=10000, z_cutoff=0.07, feet
 			pred_all = Meshes(pred_v, pred_f)
 			got = eval_3d_metrics(pred_all, gt_all, pred_verts=pred_verts, template_kp_idxs=kp_t, gt_kps=gt_kps, samples=samples, z_cutoff=z_cutoff,
 								  return_samples=True, **(dict(surface=True) if surface else {}), **(dict(measurements=spec) if spec is not None else {}),
-								  **(dict(align=align) if align is not None else {}),
-								  **(dict(return_per_foot=True) if surface or spec is not None or align is not None else {}))
+								  **(dict(align=align) if align is not None else {}), **(dict(volume=volume) if volume is not None else {}),
+								  **(dict(return_per_foot=True) if surface or spec is not None or align is not None or volume is not None else {}))
 			metrics, (_, pred_pts) = got[0], got[1]
-			surf_per_foot = got[2] if surface or spec is not None or align is not None else {}
+			surf_per_foot = got[2] if surface or spec is not None or align is not None or volume is not None else {}
 			per_foot = torch.norm(pred_verts[:, kp_t] - gt_kps, dim=-1) * 1e3
 			written = {}
 			if produce_spins:
@@ -198,7 +201,7 @@ def eval_3d(model, dataset, template_kp_idxs, samples=10000, z_cutoff=0.07, feet
 	finally:
 		model.train(was_training)
 	out = {k: float(metrics[k]) for k in ('Keypoint (mm)', f'Chamf z-cutoff {z_cutoff} (μm)', 'Chamf (μm)') + (('Scan→pred (mm)', 'Pred→scan (mm)', 'Surf (μm)') if surface else ())
-		   + (measurement_names(spec) if spec is not None else ()) + (('Chamf aligned (μm)', 'Keypoint aligned (mm)') if align is not None else ())}
+		   + (measurement_names(spec) if spec is not None else ()) + (('Chamf aligned (μm)', 'Keypoint aligned (mm)') if align is not None else ()) + (('Vol IoU (%)', 'Volume err (ml)') if volume is not None else ())}
 	if not (return_per_foot or render_correspondences or keep_meshes):
 		return out
 	extra = dict(written)
@@ -210,6 +213,8 @@ def eval_3d(model, dataset, template_kp_idxs, samples=10000, z_cutoff=0.07, feet
 			extra['measure_pred_mm'], extra['measure_gt_mm'] = surf_per_foot['measure_pred_mm'], surf_per_foot['measure_gt_mm']
 		if align is not None:
 			extra.update({k: surf_per_foot[k] for k in ('align_R', 'align_T', 'align_s', 'align_rmse')})
+		if volume is not None:
+			extra.update({k: surf_per_foot[k] for k in ('vol_iou', 'volume_pred_ml', 'volume_gt_ml')})
 	if render_correspondences:
 		extra.update({k: torch.cat(v) for k, v in images.items()})
 	return out, extra

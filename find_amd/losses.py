@@ -257,6 +257,27 @@ class SurfaceDistanceLoss(nn.Module):
 		return (to_pred.mean(1) + to_gt.mean(1)).mean()
 
 
+class PenetrationLoss(nn.Module):
+	"""Penalty for points inside a mesh (not in the reference): a foot's vertices against a shoe last, or against a ground slab.  The mean
+	over the points of [w > level] d2, with d2 the exact squared distance to the mesh's surface (functional.point_face_distance) and w the
+	point's winding number about the mesh (find_amd.inside.winding_number): points outside cost nothing, a point inside its squared depth.
+	m^2, like the Chamfer term.  The gradient reaches the points and the mesh's vertices through d2; which points are inside is a constant."""
+
+	def __init__(self, level=0.5):
+		super().__init__()
+		self.level = level
+
+	def forward(self, points, meshes: Meshes, lengths=None):
+		"""points (N, P, 3) against mesh n of meshes (shared or ragged faces); lengths (N): the point counts of a padded batch, whose rows at
+		or past them do not count.  sum over the inside points of d2 / the number of points that count."""
+		from . import inside
+		verts, faces = meshes.verts_padded(), _mesh_faces(meshes)
+		dist2, _, _ = FN.point_face_distance(points, verts, faces, lengths)
+		w = inside.winding_number(points, verts, faces, lengths)
+		n = max(points.shape[0] * points.shape[1], 1) if lengths is None else torch.as_tensor(lengths).sum().clamp(min=1).to(dist2.device)
+		return torch.where(w > self.level, dist2, torch.zeros_like(dist2)).sum() / n
+
+
 class ARAPLoss(nn.Module):
 	"""As-rigid-as-possible deformation energy against a rest mesh (not in the reference; Sorkine & Alexa 2007): every vertex neighbourhood
 	of the deformed mesh should be a rotated copy of the rest mesh's, so bending is free and stretch and shear are not.  One HIP pass each

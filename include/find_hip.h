@@ -222,7 +222,8 @@ int find_linear_wgrad(find_ctx* ctx, const float* dz, const float* x, int64_t n_
  * uniform grid from 64 points per cloud on, 16384 the balanced tiles from 64 points per cloud on (up to 8192), 32768 never the tiles
  * (geom.hip; tests/test_gpu_chamfer_tiles.py); 2048 / 4096 the band / the candidate-list rasteriser at every image size (default: the
  * band kernel from 384^2 pixels on, csrc/render_band.h -- the two agree in everything but the last bits of the alpha products); 8192
- * find_point_face_fwd never splits a mesh's faces over several workgroups (surface.hip; tests/test_gpu_surface.py); the field 0x70000, when
+ * find_point_face_fwd and find_winding_fwd never split a mesh's faces over several workgroups (surface.hip, winding.hip;
+ * tests/test_gpu_surface.py, tests/test_gpu_inside.py); the field 0x70000, when
  * k = (bits >> 16) & 7 is not 0: find_chamfer_surface_bwd cuts every foot into 1 << (k - 1) slices, whatever its size rule says
  * (tests/test_gpu_surface_chamfer_bwd.py).  Any other bit is refused (FIND_EINVAL). */
 int find_render_switches(int64_t bits);
@@ -882,6 +883,24 @@ int find_arap_fwd(const float* verts, const float* rest, const int32_t* nbr_off,
 				  int64_t n_nbr, double w_sum, double* R, float* cell, float* energy, int32_t* degenerate, void* ws, int64_t ws_bytes, void* stream);
 int find_arap_bwd(const float* verts, const float* rest, const int32_t* nbr_off, const int32_t* nbr_idx, const float* nbr_w, int64_t n, int64_t v,
 				  int64_t n_nbr, double w_sum, const double* R, const float* g, float* d_verts, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Generalised winding numbers (winding.hip; Jacobson et al. 2013).  Not in the reference.  points (N, P, 3) with per-mesh counts p_len (N)
+ * int32 (NULL = all P); verts (N, V, 3); faces (faces_batch, F, 3) int32, faces_batch 1 (shared) or N (per mesh, rows of -1 pad the shorter
+ * ones), as find_point_face_fwd.  P = 0 and F = 0 are allowed.
+ * find_winding_fwd: w (N, P) = sum over the faces of mesh n of Omega / 4 pi, with A = a - p, B = b - p, C = c - p formed in float32,
+ *   det = A . (B x C) (every product rounded on its own), den = |A||B||C| + (A.B)|C| + (B.C)|A| + (C.A)|B|, Omega = 2 atan2f(det, den).
+ *   Exactly 0, never NaN: a -1 row, a face with an index outside [0, V), a face with a corner at the query, a face with det == 0.  Rows at
+ *   or past p_len[n], and a mesh without such a face, get 0.  No gradient.  The sum is in double, without atomics, in an order that depends
+ *   on F alone: faces in runs of 128 in face order, eight runs to a chunk of 1024 faces, the chunks in order (csrc/winding_math.h:
+ *   ordered_sum).  Two runs agree bit for bit; a row does not depend on N, P or its position, nor on whether the chunks went to workgroups
+ *   of their own (they do when ceil(P / 128) N < 2048 and 2 <= ceil(F / 1024) <= 64; never under bit 8192 of find_render_switches).
+ *   ws: find_winding_ws_bytes(N, P, F) bytes, 8-byte aligned (-1 for bad sizes: N >= 65536, P, F >= 2^30), free again when the call's work
+ *   is done.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t find_winding_ws_bytes(int64_t n_meshes, int64_t n_points, int64_t n_faces);
+int find_winding_fwd(const float* points, const int32_t* p_len, const float* verts, const int32_t* faces, int64_t faces_batch, int64_t n_meshes,
+					 int64_t n_points, int64_t n_verts, int64_t n_faces, float* w, void* ws, int64_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Fused multi-tensor optimiser steps.  Replace torch.optim.Adam / torch.optim.SGD(momentum=0.9)
