@@ -903,7 +903,43 @@ int find_winding_fwd(const float* points, const int32_t* p_len, const float* ver
 					 int64_t n_points, int64_t n_verts, int64_t n_faces, float* w, void* ws, int64_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
- * Fused multi-tensor optimiser steps.  Replace torch.optim.Adam / torch.optim.SGD(momentum=0.9)
+ * Iso-surface extraction by surface nets (surface_nets.hip; Gibson 1998).  Not in the reference.  values (N, nx, ny, nz) float32, sample
+ * (i, j, k) at flat index (i ny + j) nz + k, every axis 2 .. 1024 samples, one `iso` per call.
+ *   Sides: a sample is inside iff value < iso, compared exactly, and the value is finite (value == iso, NaN, +-inf: outside).
+ *   Cells: cell (i, j, k) covers samples i..i+1, j..j+1, k..k+1, flat index (i (ny-1) + j) (nz-1) + k; corner c = 4 di + 2 dj + dk; the 12
+ *     edges (a, b), a < b, join corners that differ in one bit, in lexicographic order; a cell is active iff its corners are not all on one side.
+ *   Vertex: on a crossing edge t = (iso - v_a) / (v_b - v_a) in float32 (0.5 if not finite), p = corner_a + t (corner_b - corner_a);
+ *     g = (i, j, k) + (sum of p in edge order) / n, n the number of crossing edges: GRID coordinates (the caller forms
+ *     origin + (g + 0.5) spacing).  Vertices are numbered in flat cell order.
+ *   Faces: lattice edges in flat sample order, per sample +x, +y, +z.  The edge along ax from sample s emits a quad iff its ends differ in
+ *     side and 1 <= s_u <= n_u - 2, 1 <= s_w <= n_w - 2 for u = (ax+1) % 3, w = (ax+2) % 3: the vertices of the cells s + du e_u + dw e_w,
+ *     (du, dw) = (-1,-1), (0,-1), (0,0), (-1,0), reversed if s is not inside; triangles (q0, q1, q2), (q0, q2, q3).  Normals point outside.
+ *   status (N) int32: 1 an active cell in the outermost cell layer (the mesh is open there); 2 / 4 vertex / face capacity exceeded; 8 a
+ *     non-finite sample.  Closed away from the grid boundary; 2-manifold only where no lattice face has four sign changes.
+ * find_surface_nets_count writes n_verts, n_faces (N) int64 and status (bits 1 and 8), and leaves the per-block counts (blocks of
+ *   FIND_SURFACE_NETS_BLOCK samples / cells) and their exclusive scans in ws.
+ * find_surface_nets_emit, with the SAME ws and the counts of the count call: g (N, vcap, 3) float32, faces (N, fcap, 3) int32, the
+ *   cell -> vertex map (N, cells) int32 (-1: no vertex) at the START of ws, and bits 2 / 4 of status.  Rows at or past a mesh's count: 0 (g),
+ *   -1 (faces).  Nothing at or past vcap / fcap is written; on overflow the counts stay the true ones and that mesh's rows are unspecified.
+ * find_surface_nets_bwd: grad_values (N, nx, ny, nz) and grad_iso (N) float32 from grad_g (N, vcap, 3) = d L / d g and the map: one gather
+ *   per sample; d = v_b - v_a, dt/dv_a = (iso - v_b) / d^2, dt/dv_b = -(iso - v_a) / d^2, dt/diso = 1 / d, n constant; grad_iso is summed
+ *   in double in a fixed order.  Vertices at or past vcap have no gradient.
+ * No atomics anywhere; two runs agree bit for bit; a mesh's output depends on its own grid alone.  ws: find_surface_nets_ws_bytes /
+ *   find_surface_nets_bwd_ws_bytes(N, nx, ny, nz) bytes, 8-byte aligned (-1 for bad sizes: N >= 65536, an axis outside 2 .. 1024).
+ * ---------------------------------------------------------------------------------------------- */
+#define FIND_SURFACE_NETS_BLOCK 256
+int64_t find_surface_nets_ws_bytes(int64_t n_meshes, int64_t nx, int64_t ny, int64_t nz);
+int64_t find_surface_nets_bwd_ws_bytes(int64_t n_meshes, int64_t nx, int64_t ny, int64_t nz);
+int find_surface_nets_count(const float* values, float iso, int64_t n_meshes, int64_t nx, int64_t ny, int64_t nz, int64_t* n_verts, int64_t* n_faces,
+							int32_t* status, void* ws, int64_t ws_bytes, void* stream);
+int find_surface_nets_emit(const float* values, float iso, int64_t n_meshes, int64_t nx, int64_t ny, int64_t nz, const int64_t* n_verts,
+						   const int64_t* n_faces, int64_t vcap, int64_t fcap, float* g, int32_t* faces, int32_t* status, void* ws, int64_t ws_bytes,
+						   void* stream);
+int find_surface_nets_bwd(const float* values, float iso, int64_t n_meshes, int64_t nx, int64_t ny, int64_t nz, const int32_t* cellmap,
+						  const float* grad_g, int64_t vcap, float* grad_values, float* grad_iso, void* ws, int64_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Fused multi-tensor optimiser steps. Replace torch.optim.Adam / torch.optim.SGD(momentum=0.9)
  * as constructed by the reference (src/train/train.py:161-168) and stepped once per batch
  * (src/train/trainer.py:121-123).  `param`, `grad`, moment arrays: HOST arrays of n_tensors DEVICE pointers (fp32,
  * contiguous); `numel`: host array.  Dense updates, torch's single-tensor arithmetic operation for operation;
