@@ -115,6 +115,9 @@ PROTOTYPES = {
 	'find_arap_bwd': (c_int, [_P, _P, _P, _P, _P, _I, _I, _I, c_double, _P, _P, _P, _P]),
 	'find_winding_ws_bytes': (c_int64, [_I, _I, _I]),
 	'find_winding_fwd': (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _I, _P]),
+	'find_ray_ws_bytes': (c_int64, [_I, _I, _I]),
+	'find_ray_fwd': (c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, c_float, c_float, c_int, _P, _P, _P, _P, _P, _I, _P]),
+	'find_ray_bwd': (c_int, [_P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
 	'find_surface_nets_ws_bytes': (c_int64, [_I, _I, _I, _I]),
 	'find_surface_nets_bwd_ws_bytes': (c_int64, [_I, _I, _I, _I]),
 	'find_surface_nets_count': (c_int, [_P, c_float, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P]),

@@ -135,6 +135,34 @@ def bake_colours(model, plan, shapevec=None, texvec=None, posevec=None, texels_p
 	return TexturesUV(maps, fu.to(maps.device)[None].expand(N, -1, -1), vu.to(maps.device)[None].expand(N, -1, -1))
 
 
+def texel_normals(plan, verts, faces):
+	"""The covered texels' shading normals (N, T, 3): the barycentric blend of functional.vertex_normals at the texel's face, as
+	BakePlan.points blends the positions (not renormalised; rays.ambient_occlusion normalises what it is given)."""
+	vn = FN.vertex_normals(verts, faces)
+	if faces.dim() == 3:
+		faces = faces[0]
+	corners = faces.long()[plan._face_idx]
+	b = plan._bary_idx
+	return sum(b[None, :, k, None] * vn[:, corners[:, k]] for k in range(3))
+
+
+def bake_ambient_occlusion(plan, verts, faces, n_dirs=64, max_dist=None, fill=1.0):
+	"""An ambient-occlusion map per mesh, (N, H, W, 1) in [0, 1] (1 = open sky): rays.ambient_occlusion at the covered texels' surface points
+	(plan.points) about texel_normals, each texel's rays never hitting the face that owns it (skip); the gutter and the rest of the map as
+	BakePlan.assemble.  verts (N, V, 3), faces (F, 3) (or (1, F, 3)), face for face the atlas's faces_uvs.  Multiply a baked colour map by
+	it to shade: maps * ao.  No gradient."""
+	from . import rays
+	if plan.idx.numel() == 0:
+		raise ValueError('find_amd.bake.bake_ambient_occlusion: the atlas covers no texel of the map')
+	with torch.no_grad():
+		f = faces[0] if faces.dim() == 3 else faces
+		pts = plan.points(verts, f).contiguous()
+		N = pts.shape[0]
+		skip = plan._face_idx.to(torch.int32)[None].expand(N, -1)
+		ao = rays.ambient_occlusion(pts, texel_normals(plan, verts, f).contiguous(), verts, f, n_dirs=n_dirs, max_dist=max_dist, skip=skip)
+		return plan.assemble(ao[..., None], fill)
+
+
 def textured_meshes(model, plan, verts_uvs, faces_uvs, batch, is_train=False):
 	"""model.get_meshes_from_batch(batch, is_train)['meshes'] with the baked TexturesUV in place of the vertex colours (which are not
 	evaluated).  FootRenderer and vis.turntable take the result; no gradient."""

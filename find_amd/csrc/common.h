@@ -12,11 +12,11 @@
 namespace find {
 
 void set_error(const char* fmt, ...);
-extern int g_raster_ablate;  // render.hip / geom.hip / surface.hip switches (find_render_switches)
+extern int g_raster_ablate;  // render.hip / geom.hip / surface.hip / winding.hip / raycast.hip switches (find_render_switches)
 
 // result-preserving switches
 constexpr int MLP_SWITCHES = 16 | 32 | 128;              // "ablate": no s_setprio in gemm4, every column block in the Fourier dW, 32-row fused tiles
-constexpr int RASTER_SWITCHES = 8 | 16 | 256 | 512 | 1024 | 2048 | 4096 | 8192 | 16384 | 32768 | 0x70000;  // no early exit, unsorted tile lists, tiny list pool; Chamfer: all pairs / grid from 64 points; 2048 / 4096: band / list rasteriser at every size; 8192: point-face search and winding numbers never split the faces; Chamfer: 16384 / 32768: balanced tiles from 64 points / never; 0x70000: a field k > 0 = 1 << (k - 1) slices per foot in find_chamfer_surface_bwd
+constexpr int RASTER_SWITCHES = 8 | 16 | 256 | 512 | 1024 | 2048 | 4096 | 8192 | 16384 | 32768 | 0x70000;  // no early exit, unsorted tile lists, tiny list pool; Chamfer: all pairs / grid from 64 points; 2048 / 4096: band / list rasteriser at every size; 8192: point-face search, winding numbers and ray casting never split the faces; Chamfer: 16384 / 32768: balanced tiles from 64 points / never; 0x70000: a field k > 0 = 1 << (k - 1) slices per foot in find_chamfer_surface_bwd
 
 inline int check_launch(const char* what) {
 	hipError_t e = hipGetLastError();

@@ -222,8 +222,8 @@ int find_linear_wgrad(find_ctx* ctx, const float* dz, const float* x, int64_t n_
  * uniform grid from 64 points per cloud on, 16384 the balanced tiles from 64 points per cloud on (up to 8192), 32768 never the tiles
  * (geom.hip; tests/test_gpu_chamfer_tiles.py); 2048 / 4096 the band / the candidate-list rasteriser at every image size (default: the
  * band kernel from 384^2 pixels on, csrc/render_band.h -- the two agree in everything but the last bits of the alpha products); 8192
- * find_point_face_fwd and find_winding_fwd never split a mesh's faces over several workgroups (surface.hip, winding.hip;
- * tests/test_gpu_surface.py, tests/test_gpu_inside.py); the field 0x70000, when
+ * find_point_face_fwd, find_winding_fwd and find_ray_fwd never split a mesh's faces over several workgroups (surface.hip, winding.hip,
+ * raycast.hip; tests/test_gpu_surface.py, tests/test_gpu_inside.py, tests/test_gpu_rays.py); the field 0x70000, when
  * k = (bits >> 16) & 7 is not 0: find_chamfer_surface_bwd cuts every foot into 1 << (k - 1) slices, whatever its size rule says
  * (tests/test_gpu_surface_chamfer_bwd.py).  Any other bit is refused (FIND_EINVAL). */
 int find_render_switches(int64_t bits);
@@ -901,6 +901,37 @@ int find_arap_bwd(const float* verts, const float* rest, const int32_t* nbr_off,
 int64_t find_winding_ws_bytes(int64_t n_meshes, int64_t n_points, int64_t n_faces);
 int find_winding_fwd(const float* points, const int32_t* p_len, const float* verts, const int32_t* faces, int64_t faces_batch, int64_t n_meshes,
 					 int64_t n_points, int64_t n_verts, int64_t n_faces, float* w, void* ws, int64_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Ray casting (raycast.hip; the watertight test of Woop, Benthin & Wald 2013).  Not in the reference.  origins, dirs (N, R, 3) with per-mesh
+ * counts r_len (N) int32 (NULL = all R); skip (N, R) int32 (NULL = none): a face the ray never hits (the face its origin lies on); verts,
+ * faces, faces_batch as find_winding_fwd.  R = 0 and F = 0 are allowed.  d need not be normalised: t is in units of |d|.
+ * The pair test, every product and sum rounded on its own in the order of csrc/raycast_math.h (which tests/rays_ref.py restates):
+ *   per ray   kz = argmax |d| (the first of equals), kx, ky the next two axes in cyclic order, swapped if d[kz] < 0;
+ *             e1 = axis(kx) - (d[kx] / d[kz]) axis(kz), e2 = axis(ky) - (d[ky] / d[kz]) axis(kz), dd = d . d
+ *   per corner P = p - o, x = (P0 e1_0 + P1 e1_1) + P2 e1_2, y likewise with e2: the same bits in every face that uses the vertex
+ *   per pair  U = cx by - cy bx, V = ax cy - ay cx, W = bx ay - by ax, det = (U + V) + W; inside: all three >= 0 or all three <= 0, det != 0;
+ *             t = ((U za + V zb) + W zc) / (det dd) with z = P . d; barycentrics (U, V, W) / det; a hit: t_min < t <= t_max, t finite.
+ *   Never a hit: a -1 row, a face with an index outside [0, V), a face with a corner at the origin (P == 0), the ray's skip face, a ray with a
+ *   non-finite component or d == 0.  Among equal t the smallest face index wins.  A computed sign is right or zero, and a zero is inside:
+ *   a ray through a shared edge or a vertex of a closed mesh hits; there is no double-precision fallback.
+ * find_ray_fwd, any_hit = 0: t (N, R), idx (N, R) int32, bary (N, R, 3); a miss, and a row at or past r_len, gives +inf, -1, 0 0 0.  hit may
+ *   be NULL.  any_hit = 1: hit (N, R) uint8 alone, equal to isfinite(t) of the other call; t, idx, bary may be NULL.  Every row is written.
+ *   Results are 64-bit keys (t bits << 32 | face) merged by integer minimum, no float atomics: two runs agree bit for bit, and a row does not
+ *   depend on N, R, its position, nor on whether the face range was split over workgroups (it is, in up to 16 pieces of at least 1024 faces,
+ *   while ceil(R / 128) N pieces < 1024; never under bit 8192 of find_render_switches).  t_min >= 0 is required.
+ *   ws: find_ray_ws_bytes(N, R, F) bytes, 8-byte aligned (-1 for bad sizes: N >= 65536, R, F >= 2^30), free again when the call's work is done.
+ * find_ray_bwd: with n = (b - a) x (c - a), g = n . d, w the stored barycentrics: d_origins = -d_t n / g, d_dirs = -d_t t n / g, both
+ *   (N, R, 3), OVERWRITTEN in every row (0 for a miss); d_verts (N, V, 3) += d_t w_i n / g at the hit face's corners, with float atomics into a
+ *   buffer the CALLER ZEROED (the contract of find_point_face_bwd).  The face and the barycentrics are constants.  Any of the three may be NULL.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t find_ray_ws_bytes(int64_t n_meshes, int64_t n_rays, int64_t n_faces);
+int find_ray_fwd(const float* origins, const float* dirs, const int32_t* r_len, const int32_t* skip, const float* verts, const int32_t* faces,
+				 int64_t faces_batch, int64_t n_meshes, int64_t n_rays, int64_t n_verts, int64_t n_faces, float t_min, float t_max, int any_hit,
+				 float* t, int32_t* idx, float* bary, uint8_t* hit, void* ws, int64_t ws_bytes, void* stream);
+int find_ray_bwd(const float* origins, const float* dirs, const float* verts, const int32_t* faces, int64_t faces_batch, const int32_t* idx,
+				 const float* bary, const float* t, const float* d_t, int64_t n_meshes, int64_t n_rays, int64_t n_verts, int64_t n_faces,
+				 float* d_origins, float* d_dirs, float* d_verts, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Iso-surface extraction by surface nets (surface_nets.hip; Gibson 1998).  Not in the reference.  values (N, nx, ny, nz) float32, sample
