@@ -8,6 +8,9 @@ builds in src/train/train.py:161-168 --
 Same constructor keywords, param_groups, state keys ('step', 'exp_avg', 'exp_avg_sq' / 'momentum_buffer') and state_dict layout
 as torch.optim, so checkpoints and schedulers keep working; step() updates every tensor of a param group in ONE launch of
 libfind_hip.so (find_adam_step / find_sgd_step).  Dense updates with torch's arithmetic; amsgrad / maximize are not provided.
+Adam's default path and SGD: hyper-parameters go to the library as Python floats (doubles) and are rounded there where torch rounds them; a
+parameter of 0 elements is stepped as torch steps it: its state is made and counted, and the library skips it (its NULL data_ptr() is
+accepted for numel 0).  Adam(capturable=True) still hands fp32 hyper-parameters over and refuses a 0-element parameter.
 There is no CPU fallback: parameters must live on the GPU."""
 import ctypes
 
@@ -153,16 +156,17 @@ class SGD(torch.optim.Optimizer):
 			if not ps:
 				continue
 			mom = group['momentum']
-			# tensors without a buffer yet take torch's "clone the gradient" first step
-			fresh = [p for p in ps if mom != 0 and 'momentum_buffer' not in self.state[p]]
-			seasoned = [p for p in ps if not (mom != 0 and 'momentum_buffer' not in self.state[p])]
+			# tensors without a buffer yet take torch's "clone the gradient" first step; a state entry momentum_buffer = None (torch's own
+			# state dicts can hold one) is no buffer yet, as in torch
+			fresh = [p for p in ps if mom != 0 and self.state[p].get('momentum_buffer') is None]
+			seasoned = [p for p in ps if not (mom != 0 and self.state[p].get('momentum_buffer') is None)]
 			for first, plist in ((True, fresh), (False, seasoned)):
 				if not plist:
 					continue
 				bufs = None
 				if mom != 0:
 					for p in plist:
-						if 'momentum_buffer' not in self.state[p]:
+						if self.state[p].get('momentum_buffer') is None:
 							self.state[p]['momentum_buffer'] = torch.empty_like(p, memory_format=torch.preserve_format)
 					bufs = [self.state[p]['momentum_buffer'] for p in plist]
 				grads = [p.grad if p.grad.is_contiguous() else p.grad.contiguous() for p in plist]

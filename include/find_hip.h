@@ -975,19 +975,25 @@ int find_surface_nets_bwd(const float* values, float iso, int64_t n_meshes, int6
  * (src/train/trainer.py:121-123).  `param`, `grad`, moment arrays: HOST arrays of n_tensors DEVICE pointers (fp32,
  * contiguous); `numel`: host array.  Dense updates, torch's single-tensor arithmetic operation for operation;
  * amsgrad / maximize / foreach-only options are not provided.
+ * find_adam_step, find_sgd_step: hyper-parameters are doubles, as torch's Python floats are, and each is rounded to fp32 once, where
+ * torch rounds it: 1 - beta1, 1 - beta2, 1 - dampening and lr / bias_correction1 are formed in double first.  A tensor with numel == 0
+ * is accepted and skipped: its pointers (param, grad, moments) may be NULL, as the data_ptr() of a 0-element device tensor is.  For every
+ * other tensor a NULL pointer is refused.  All tensors and hyper-parameters are checked before the first launch: a call that returns an
+ * error has updated nothing.
  * find_adam_step: `step` is the 1-based count INCLUDING this update (torch's state['step'] after it).
- * find_sgd_step: `first_step` != 0 initialises the momentum buffers to the gradient (torch clones it).
+ * find_sgd_step: `first_step` != 0 initialises the momentum buffers to the gradient (torch clones it, dampening ignored).
  * ---------------------------------------------------------------------------------------------- */
 int find_adam_step(int64_t n_tensors, float* const* param, const float* const* grad, float* const* exp_avg, float* const* exp_avg_sq,
-				   const int64_t* numel, float lr, float beta1, float beta2, float eps, float weight_decay, int64_t step, void* stream);
+				   const int64_t* numel, double lr, double beta1, double beta2, double eps, double weight_decay, int64_t step, void* stream);
  /* find_adam_step_dev: the same update with the step count on the DEVICE -- `step_dev` points to one fp32 holding the 1-based count
  * including this update (the caller increments it on `stream` first), and the bias corrections are formed on the device in fp32, as
  * torch.optim.Adam(capturable=True) does: nothing step-dependent is baked into the launch, so the call can be captured in a HIP graph
- * and replayed (find_amd/graph.py). */
+ * and replayed (find_amd/graph.py).  This entry point still takes fp32 hyper-parameters and forms 1 - beta in fp32, refuses a NULL pointer
+ * whatever the tensor's numel, and checks the tensors launch by launch (48 at a time). */
 int find_adam_step_dev(int64_t n_tensors, float* const* param, const float* const* grad, float* const* exp_avg, float* const* exp_avg_sq,
 					   const int64_t* numel, float lr, float beta1, float beta2, float eps, float weight_decay, const float* step_dev, void* stream);
 int find_sgd_step(int64_t n_tensors, float* const* param, const float* const* grad, float* const* momentum_buf, const int64_t* numel,
-				  float lr, float momentum, float dampening, float weight_decay, int nesterov, int first_step, void* stream);
+				  double lr, double momentum, double dampening, double weight_decay, int nesterov, int first_step, void* stream);
 
 #ifdef __cplusplus
 }
