@@ -118,6 +118,11 @@ PROTOTYPES = {
 	'find_ray_ws_bytes': (c_int64, [_I, _I, _I]),
 	'find_ray_fwd': (c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, c_float, c_float, c_int, _P, _P, _P, _P, _P, _I, _P]),
 	'find_ray_bwd': (c_int, [_P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
+	'find_bvh_bytes': (c_int64, [_I, _I]),
+	'find_bvh_keys': (c_int, [_P, _P, _I, _I, _I, _I, _P, _P, _I, _P]),
+	'find_bvh_build': (c_int, [_P, _P, _I, _I, _I, _I, _P, _P, _I, _P]),
+	'find_bvh_refit': (c_int, [_P, _P, _I, _I, _I, _I, _P, _I, _P]),
+	'find_ray_bvh_fwd': (c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, c_float, c_float, c_int, _P, _P, _P, _P, _P, _I, _P, _I, _P]),
 	'find_surface_nets_ws_bytes': (c_int64, [_I, _I, _I, _I]),
 	'find_surface_nets_bwd_ws_bytes': (c_int64, [_I, _I, _I, _I]),
 	'find_surface_nets_count': (c_int, [_P, c_float, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P]),

@@ -16,6 +16,7 @@ from . import _lib
 from . import functional as FN
 from ._lib import check, current_stream, ptr
 from .functional import _c, _faces_i32, _require_gpu
+from .rays import _accel_keyword
 from .structures import TexturesUV
 
 
@@ -146,11 +147,13 @@ def texel_normals(plan, verts, faces):
 	return sum(b[None, :, k, None] * vn[:, corners[:, k]] for k in range(3))
 
 
+@_accel_keyword
 def bake_ambient_occlusion(plan, verts, faces, n_dirs=64, max_dist=None, fill=1.0):
 	"""An ambient-occlusion map per mesh, (N, H, W, 1) in [0, 1] (1 = open sky): rays.ambient_occlusion at the covered texels' surface points
 	(plan.points) about texel_normals, each texel's rays never hitting the face that owns it (skip); the gutter and the rest of the map as
 	BakePlan.assemble.  verts (N, V, 3), faces (F, 3) (or (1, F, 3)), face for face the atlas's faces_uvs.  Multiply a baked colour map by
-	it to shade: maps * ao.  No gradient."""
+	it to shade: maps * ao.  Keyword accel (added by rays._accel_keyword): None, 'bvh' or a rays.MeshBVH of (verts, faces (F, 3)), as in
+	rays.ray_mesh_intersect: the same bits, found through a bounding-volume hierarchy instead of against every face.  No gradient."""
 	from . import rays
 	if plan.idx.numel() == 0:
 		raise ValueError('find_amd.bake.bake_ambient_occlusion: the atlas covers no texel of the map')

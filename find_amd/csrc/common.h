@@ -13,6 +13,12 @@ namespace find {
 
 void set_error(const char* fmt, ...);
 extern int g_raster_ablate;  // render.hip / geom.hip / surface.hip / winding.hip / raycast.hip switches (find_render_switches)
+namespace raycast {
+// raycast.hip: the launch that ends find_ray_fwd and find_ray_bvh_fwd (t, idx, bary or hit from the winning keys)
+int ray_finish_launch(const float* origins, const float* dirs, const int32_t* r_len, const float* verts, const int32_t* faces, int64_t faces_mesh_stride,
+					  int64_t n_meshes, int64_t n_rays, int64_t n_verts, int64_t n_faces, const unsigned long long* key, float* t, int32_t* idx, float* bary,
+					  uint8_t* hit, void* stream);
+}  // namespace raycast
 
 // result-preserving switches
 constexpr int MLP_SWITCHES = 16 | 32 | 128;              // "ablate": no s_setprio in gemm4, every column block in the Fourier dW, 32-row fused tiles

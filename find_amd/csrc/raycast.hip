@@ -240,6 +240,16 @@ static int face_splits(int64_t blocks, int64_t n_faces) {
 	return splits;
 }
 
+// The last launch of find_ray_fwd and of find_ray_bvh_fwd (bvh.hip): t, idx, bary -- or hit alone when hit != NULL -- from the keys.
+int ray_finish_launch(const float* origins, const float* dirs, const int32_t* r_len, const float* verts, const int32_t* faces, int64_t faces_mesh_stride,
+					  int64_t n_meshes, int64_t n_rays, int64_t n_verts, int64_t n_faces, const unsigned long long* key, float* t, int32_t* idx, float* bary,
+					  uint8_t* hit, void* stream) {
+	hipLaunchKernelGGL(ray_finish_kernel, dim3((unsigned)cdiv(n_rays, 256), (unsigned)n_meshes), dim3(256), 0, (hipStream_t)stream, origins, dirs, r_len, verts,
+					   faces, faces_mesh_stride, (int)n_rays, (int)n_verts, (int)n_faces, n_faces > 0 ? 1 : 0, key, t, idx, bary, hit);
+	FIND_LAUNCH_CHECK("ray_finish_kernel");
+	return FIND_OK;
+}
+
 }  // namespace raycast
 }  // namespace find
 
@@ -284,10 +294,7 @@ extern "C" int find_ray_fwd(const float* origins, const float* dirs, const int32
 							   splits, t_min, t_max, key);
 		FIND_LAUNCH_CHECK("ray_kernel");
 	}
-	hipLaunchKernelGGL(ray_finish_kernel, dim3((unsigned)cdiv(n_rays, 256), (unsigned)n_meshes), dim3(256), 0, s, origins, dirs, r_len, verts, faces, stride,
-					   (int)n_rays, (int)n_verts, (int)n_faces, n_faces > 0 ? 1 : 0, key, t, idx, bary, any_hit ? hit : (uint8_t*)nullptr);
-	FIND_LAUNCH_CHECK("ray_finish_kernel");
-	return FIND_OK;
+	return ray_finish_launch(origins, dirs, r_len, verts, faces, stride, n_meshes, n_rays, n_verts, n_faces, key, t, idx, bary, any_hit ? hit : (uint8_t*)nullptr, stream);
 }
 
 extern "C" int find_ray_bwd(const float* origins, const float* dirs, const float* verts, const int32_t* faces, int64_t faces_batch, const int32_t* idx,

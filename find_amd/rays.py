@@ -2,10 +2,13 @@
 csrc/raycast.hip: the watertight pair test of Woop, Benthin & Wald 2013, every ray against every face), and what follows from them --
 which vertices a camera sees, and ambient occlusion at points and at vertices.  Not in the reference.  d need not be normalised: t is in
 units of |d|, and o + t[..., None] * d is the hit point.  A ray through a shared edge or a vertex of a closed mesh hits (a zero of an edge
-function counts as inside); a face with a corner exactly at the origin is never hit, which is what lets rays start AT vertices.  There is no
+function counts as inside); a face with a corner exactly at the origin is never hit, which is what lets rays start AT vertices.  accel= gives the same bits through a bounding-volume hierarchy over the
+faces (MeshBVH, build_bvh; find_ray_bvh_fwd, csrc/bvh.hip) instead of against every face.  There is no
 CPU or eager fallback: CPU tensors raise.  The workspace comes from functional._ws and the outputs are torch.empty, which the kernels write
 in full (tests/test_gpu_rays.py runs the module over poisoned memory)."""
+import functools
 import math
+import threading
 
 import torch
 
@@ -14,6 +17,7 @@ from . import functional as FN
 from ._lib import check, current_stream, ptr
 
 _CHUNK_RAYS = 1 << 20   # rays of all meshes together that vertex_visibility generates and consumes at a time
+BVH_LEAF, BVH_ARITY = 4, 4   # faces per leaf and children per node of a MeshBVH (FIND_BVH_LEAF, FIND_BVH_ARITY of include/find_hip.h)
 
 
 def _check(who, origins, dirs, verts, faces):
@@ -52,13 +56,96 @@ def _per_ray(who, name, x, N, R, dev):
 	return x
 
 
+class MeshBVH:
+	"""A bounding-volume hierarchy over the faces of a batch of meshes (find_bvh_keys / find_bvh_build / find_bvh_refit, csrc/bvh.hip): what
+	accel= of this module's functions takes.  Opaque: `data` is the library's buffer (find_bvh_bytes).  It remembers N, V, F and faces_batch
+	and refuses tensors of other shapes; the faces it was built on are taken to be the faces of every later call.  After the vertices
+	change, call refit(verts) -- boxes again from the new vertices in the stored order, no sort; exact however far they moved, only the
+	speed depends on the order -- or the answers are wrong (never a fault: every index in the structure is computed or range-checked)."""
+
+	def __init__(self, N, V, F, faces_batch, faces, data):
+		self.N, self.V, self.F, self.faces_batch, self.faces, self.data = N, V, F, faces_batch, faces, data
+
+	@property
+	def nbytes(self):
+		return self.data.numel()
+
+	def _fits(self, who, N, V, F, fb, dev):
+		if (N, V, F, fb) != (self.N, self.V, self.F, self.faces_batch) or dev != self.data.device:
+			raise RuntimeError(f'find_amd.rays.{who}: this MeshBVH was built for N, V, F, faces_batch = {(self.N, self.V, self.F, self.faces_batch)} on '
+							   f'{self.data.device}, got {(N, V, F, fb)} on {dev}')
+
+	def refit(self, verts):
+		"""The boxes again from `verts` (N, V, 3), with the faces of the build (self.faces, int32).  Returns self."""
+		N, V, F, fb = _check_mesh('MeshBVH.refit', verts, self.faces)
+		self._fits('MeshBVH.refit', N, V, F, fb, verts.device)
+		verts = verts.detach().contiguous()
+		check(_lib.lib().find_bvh_refit(ptr(verts), ptr(self.faces), fb, N, V, F, ptr(self.data), self.data.numel(), current_stream(verts.device)),
+			  'find_bvh_refit')
+		return self
+
+
+def _check_mesh(who, verts, faces):
+	"""(N, V, F, faces_batch) of verts (N, V, 3) and faces, as _check sees them."""
+	if verts.dim() != 3 or verts.shape[-1] != 3:
+		raise RuntimeError(f'find_amd.rays.{who}: verts (N, V, 3) expected, got {tuple(verts.shape)}')
+	N, _, V, F, fb = _check(who, verts, verts, verts, faces)   # (verts stands in for the rays)
+	return N, V, F, fb
+
+
+def build_bvh(verts, faces):
+	"""A MeshBVH of verts (N, V, 3) and faces (F, 3) shared or (N, Fmax, 3) with -1 rows: Morton keys of the faces' centroids (find_bvh_keys),
+	torch.sort of every row (the keys are below 2^63, so the signed sort is the unsigned one), the boxes bottom-up (find_bvh_build).  No
+	gradient, no CPU fallback."""
+	who = 'build_bvh'
+	N, V, F, fb = _check_mesh(who, verts, faces)
+	verts, faces = verts.detach().contiguous(), FN._faces_i32(faces)
+	L = _lib.lib()
+	dev = verts.device
+	data = torch.empty(L.find_bvh_bytes(N, F), device=dev, dtype=torch.uint8)
+	keys = torch.empty(N, F, device=dev, dtype=torch.int64)
+	s = current_stream(dev)
+	check(L.find_bvh_keys(ptr(verts), ptr(faces), fb, N, V, F, ptr(keys), ptr(data), data.numel(), s), 'find_bvh_keys')
+	keys = torch.sort(keys, dim=1)[0].contiguous()
+	check(L.find_bvh_build(ptr(verts), ptr(faces), fb, N, V, F, ptr(keys), ptr(data), data.numel(), s), 'find_bvh_build')
+	return MeshBVH(N, V, F, fb, faces, data)
+
+
+_STATE = threading.local()   # .accel: what the accel= keyword of the call in progress on this thread asked for ('bvh' until the first cast builds it)
+
+
+def _accel_keyword(fn):
+	"""Gives a public function the keyword accel=None | 'bvh' | MeshBVH.  The function's own parameters stay the ones it has without the
+	keyword (tests/test_rays_host.py pins those lists, and inspect.signature reports them: accel is this wrapper's, documented in each
+	docstring).  The request travels to _cast in _STATE for the time of the call, so the functions that cast in chunks, or through one
+	another, share one structure; with accel=None the function is called as it always was."""
+	@functools.wraps(fn)
+	def call(*args, accel=None, **kw):
+		if accel is None:
+			return fn(*args, **kw)
+		if not (isinstance(accel, MeshBVH) or (isinstance(accel, str) and accel == 'bvh')):
+			raise RuntimeError(f"find_amd.rays.{fn.__name__}: accel None, 'bvh' or a MeshBVH expected, got {accel!r}")
+		before = getattr(_STATE, 'accel', None)
+		_STATE.accel = accel
+		try:
+			return fn(*args, **kw)
+		finally:
+			_STATE.accel = before
+	return call
+
+
 def _cast(who, origins, dirs, verts, faces, r_len, skip, t_min, t_max, any_hit):
-	"""One find_ray_fwd call: (t, idx, bary), or hit (N, R) bool, and the contiguous inputs it was made on."""
+	"""One find_ray_fwd call -- find_ray_bvh_fwd under accel= (_STATE) --: (t, idx, bary), or hit (N, R) bool, and the contiguous inputs it was made on."""
 	N, R, V, F, fb = _check(who, origins, dirs, verts, faces)
 	origins, dirs, verts, faces = origins.detach().contiguous(), dirs.detach().contiguous(), verts.detach().contiguous(), FN._faces_i32(faces)
 	t_min, t_max = _interval(who, t_min, t_max)
 	L = _lib.lib()
 	dev = origins.device
+	accel = getattr(_STATE, 'accel', None)
+	if isinstance(accel, str):   # 'bvh': built at the call's first cast, then shared by the rest of the call
+		accel = _STATE.accel = build_bvh(verts, faces)
+	if accel is not None:
+		accel._fits(who, N, V, F, fb, dev)
 	rl, sk = _per_ray(who, 'r_len', r_len, N, R, dev), _per_ray(who, 'skip', skip, N, R, dev)
 	ws = FN._ws(L.find_ray_ws_bytes(N, R, F), dev)
 	if any_hit:
@@ -67,8 +154,13 @@ def _cast(who, origins, dirs, verts, faces, r_len, skip, t_min, t_max, any_hit):
 	else:
 		out = (torch.empty(N, R, device=dev, dtype=torch.float32), torch.empty(N, R, device=dev, dtype=torch.int32),
 			   torch.empty(N, R, 3, device=dev, dtype=torch.float32), None)
-	check(L.find_ray_fwd(ptr(origins), ptr(dirs), ptr(rl), ptr(sk), ptr(verts), ptr(faces), fb, N, R, V, F, t_min, t_max, 1 if any_hit else 0, ptr(out[0]),
-						 ptr(out[1]), ptr(out[2]), ptr(out[3]), ptr(ws), ws.numel(), current_stream(dev)), 'find_ray_fwd')
+	if accel is None:
+		check(L.find_ray_fwd(ptr(origins), ptr(dirs), ptr(rl), ptr(sk), ptr(verts), ptr(faces), fb, N, R, V, F, t_min, t_max, 1 if any_hit else 0, ptr(out[0]),
+							 ptr(out[1]), ptr(out[2]), ptr(out[3]), ptr(ws), ws.numel(), current_stream(dev)), 'find_ray_fwd')
+	else:
+		check(L.find_ray_bvh_fwd(ptr(origins), ptr(dirs), ptr(rl), ptr(sk), ptr(verts), ptr(faces), fb, N, R, V, F, t_min, t_max, 1 if any_hit else 0, ptr(out[0]),
+								 ptr(out[1]), ptr(out[2]), ptr(out[3]), ptr(accel.data), accel.data.numel(), ptr(ws), ws.numel(), current_stream(dev)),
+			  'find_ray_bvh_fwd')
 	return (out[3].bool() if any_hit else out[:3]), (origins, dirs, verts, faces)
 
 
@@ -99,6 +191,7 @@ class _Intersect(torch.autograd.Function):
 		return d_o, d_d, d_v, None, None, None, None, None
 
 
+@_accel_keyword
 def ray_mesh_intersect(origins, dirs, verts, faces, r_len=None, skip=None, t_min=0.0, t_max=math.inf):
 	"""The closest hit of every ray on its mesh.  origins, dirs (N, R, 3), verts (N, V, 3), faces (F, 3) shared or (N, Fmax, 3) with -1 rows as
 	padding, r_len (N) ray counts or None, skip (N, R) a face per ray that it never hits (the face its origin lies on; -1: none) or None.
@@ -107,13 +200,18 @@ def ray_mesh_intersect(origins, dirs, verts, faces, r_len=None, skip=None, t_min
 	index outside [0, V), a face with a corner exactly at the origin, the skip face; a ray with a non-finite component or d == 0 hits
 	nothing.  Among equal t the smallest face wins.  Two calls agree bit for bit, and a row does not depend on the rest of the batch.
 	Differentiable in origins, dirs and verts through t (the face and the barycentrics are constants: dt/do = -n / g, dt/dd = -t n / g,
-	dt/dv_i = w_i n / g with n the face's normal and g = n . d); idx and bary carry no gradient."""
+	dt/dv_i = w_i n / g with n the face's normal and g = n . d); idx and bary carry no gradient.
+	Keyword accel (added by _accel_keyword): None -- every ray against every face --, 'bvh' -- a MeshBVH built for this call -- or a
+	MeshBVH of these meshes (build_bvh; refit after the vertices moved).  The results are the same bits and the gradients come from the same backward, with one difference: under
+	accel a face with a non-finite corner is never hit (without it that is left to the pair test, in practice a miss)."""
 	return _Intersect.apply(origins, dirs, verts, faces, r_len, skip, t_min, t_max)
 
 
+@_accel_keyword
 def ray_occluded(origins, dirs, verts, faces, r_len=None, skip=None, t_min=0.0, t_max=math.inf):
 	"""Whether each ray hits anything in (t_min, t_max]: bool (N, R), bit for bit isfinite(t) of ray_mesh_intersect with the same arguments.
-	The kernel stops walking the faces of a block of rays once all of them have hit.  No gradient."""
+	The kernel stops walking the faces of a block of rays once all of them have hit; with accel (as in ray_mesh_intersect) a ray
+	stops at its first accepted pair.  No gradient."""
 	return _cast('ray_occluded', origins, dirs, verts, faces, r_len, skip, t_min, t_max, True)[0]
 
 
@@ -123,12 +221,14 @@ def camera_centres(R, T):
 	return -(T[..., None, :] @ R.transpose(-1, -2))[..., 0, :]
 
 
+@_accel_keyword
 def vertex_visibility(verts, faces, R, T):
 	"""Which vertices each camera sees: bool (N, M, V).  verts (N, V, 3), faces as in ray_mesh_intersect, cameras R (M, 3, 3) / T (M, 3) shared
 	by the meshes or (N, M, 3, 3) / (N, M, 3), in the convention p_view = p_world @ R + T, so the centre is C = -T @ R^T.  One ray per
 	(camera, vertex) goes from C with d = v - C; the vertex is visible iff the ray hits nothing or the face it hits contains that vertex.
 	There is no tolerance: the faces at the vertex share its projected bits, so the ray hits one of them at t about 1 unless something
-	nearer is in the way.  The rays are generated and consumed a chunk of cameras at a time.  No gradient."""
+	nearer is in the way.  The rays are generated and consumed a chunk of cameras at a time; accel as in ray_mesh_intersect, the
+	structure built once for all chunks.  No gradient."""
 	who = 'vertex_visibility'
 	if verts.dim() != 3 or verts.shape[-1] != 3 or R.shape[-2:] != (3, 3) or T.shape != R.shape[:-1] or R.dim() not in (3, 4) or (R.dim() == 4 and R.shape[0] != verts.shape[0]):
 		raise RuntimeError(f'find_amd.rays.{who}: verts (N, V, 3), R (M, 3, 3) or (N, M, 3, 3) and T (M, 3) or (N, M, 3) expected, got {tuple(verts.shape)} / '
@@ -183,13 +283,15 @@ def normal_frames(normals):
 	return t1, torch.linalg.cross(n, t1), n
 
 
+@_accel_keyword
 def ambient_occlusion(points, normals, verts, faces, n_dirs=64, max_dist=None, skip=None, rays_per_call=1 << 20):
 	"""The share of n_dirs hemisphere directions about each normal that escape: (N, P) float32 in [0, 1], 1 = open sky.  points, normals
 	(N, P, 3), verts, faces as in ray_mesh_intersect; skip (N, P) the face each point lies on (never hit by its rays) or None -- a point AT a
 	vertex needs none, the faces with a corner at the origin are never hit.  max_dist: how far, in the mesh's units, a hit still occludes
 	(None: no limit).  The direction set is hemisphere_directions(n_dirs) -- fixed, cosine-distributed, so the plain share is the
 	cosine-weighted visibility -- and direction i at a point is x t1 + y t2 + z n in the frame of normal_frames(normals): the same for every
-	call.  Rays are cast by ray_occluded, at most about rays_per_call at a time.  No gradient."""
+	call.  Rays are cast by ray_occluded, at most about rays_per_call at a time; accel as in ray_mesh_intersect, the structure
+	built once for all chunks.  No gradient."""
 	who = 'ambient_occlusion'
 	if normals.shape != points.shape:
 		raise RuntimeError(f'find_amd.rays.{who}: points and normals (N, P, 3) expected, got {tuple(points.shape)} / {tuple(normals.shape)}')
@@ -218,6 +320,7 @@ def ambient_occlusion(points, normals, verts, faces, n_dirs=64, max_dist=None, s
 	return ao
 
 
+@_accel_keyword
 def vertex_ambient_occlusion(verts, faces, n_dirs=64, max_dist=None, rays_per_call=1 << 20):
 	"""ambient_occlusion at the vertices themselves, about functional.vertex_normals: (N, V).  The faces at a vertex have a corner at its rays'
 	origin and are never hit, so no skip is needed.  A vertex no face touches has no normal: its rays have d = 0, hit nothing, and it gets 1."""

@@ -934,6 +934,40 @@ int find_ray_bwd(const float* origins, const float* dirs, const float* verts, co
 				 float* d_origins, float* d_dirs, float* d_verts, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * A bounding-volume hierarchy for ray queries (bvh.hip, csrc/bvh_math.h).  Not in the reference.  verts, faces, faces_batch as find_ray_fwd.
+ * The structure is opaque: find_bvh_bytes(N, F) bytes (-1 for bad sizes: N >= 65536, F >= 2^30, a negative size), 256-byte aligned, a
+ * function of N and F alone.  Per mesh it holds the faces' order (int32) and one box per node of an implicit, complete 4-ary tree over
+ * leaves of FIND_BVH_LEAF faces in that order, the leaf count padded to a power of 4 with empty boxes; child and parent indices are computed,
+ * and every face index taken from it is range-checked, so a call on a stale or overwritten structure gives wrong answers and never a fault.
+ * A face is INVALID -- never hit, in no box -- if it is a -1 row, has an index outside [0, V), or a non-finite corner (find_ray_fwd leaves
+ * the last to the pair test); validity is decided from verts and faces at every call, not stored.
+ * find_bvh_keys: keys (N, F) uint64, morton << 32 | face: the 30-bit Morton code of the face's centroid on the box of the mesh's valid
+ *   centroids (an axis without extent: 0); an invalid face has the high word 0x7fffffff, so every key is below 2^63 and a signed 64-bit sort
+ *   orders the rows as an unsigned one does.  The head of the structure is its scratch.  No atomics.
+ * The CALLER sorts each row of keys ascending (any correct 64-bit sort: the keys of a row are distinct); the library does not sort.
+ * find_bvh_build: stores the order of the sorted keys and forms every box from verts, bottom-up, without atomics.
+ * find_bvh_refit: forms every box again from other verts (same faces, same sizes) with the stored order: no keys, no sort.  The order decides
+ *   only which faces share a box: results after a refit are exact however far the vertices moved.
+ * find_ray_bvh_fwd: find_ray_fwd's arguments, outputs, workspace (find_ray_ws_bytes) and rules, with the structure: a lane walks the tree
+ *   per ray and runs find_ray_fwd's pair test, on the same operands, on the faces of the leaves it reaches; a box is skipped only when no
+ *   pair in it can be accepted (bvh_math.h derives the margin), an equal t on a smaller face still wins, and the result does not depend on
+ *   the order of the walk: t, idx, bary and hit equal find_ray_fwd's bit for bit, except that a face with a non-finite corner is never hit.
+ *   any_hit = 1 stops a ray at its first accepted pair.  No atomics; the face range is never split.  bvh may be NULL when F = 0.
+ * ---------------------------------------------------------------------------------------------- */
+#define FIND_BVH_LEAF 4
+#define FIND_BVH_ARITY 4
+int64_t find_bvh_bytes(int64_t n_meshes, int64_t n_faces);
+int find_bvh_keys(const float* verts, const int32_t* faces, int64_t faces_batch, int64_t n_meshes, int64_t n_verts, int64_t n_faces, uint64_t* keys,
+				  void* bvh, int64_t bvh_bytes, void* stream);
+int find_bvh_build(const float* verts, const int32_t* faces, int64_t faces_batch, int64_t n_meshes, int64_t n_verts, int64_t n_faces,
+				   const uint64_t* sorted_keys, void* bvh, int64_t bvh_bytes, void* stream);
+int find_bvh_refit(const float* verts, const int32_t* faces, int64_t faces_batch, int64_t n_meshes, int64_t n_verts, int64_t n_faces, void* bvh,
+				   int64_t bvh_bytes, void* stream);
+int find_ray_bvh_fwd(const float* origins, const float* dirs, const int32_t* r_len, const int32_t* skip, const float* verts, const int32_t* faces,
+					 int64_t faces_batch, int64_t n_meshes, int64_t n_rays, int64_t n_verts, int64_t n_faces, float t_min, float t_max, int any_hit,
+					 float* t, int32_t* idx, float* bary, uint8_t* hit, const void* bvh, int64_t bvh_bytes, void* ws, int64_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Iso-surface extraction by surface nets (surface_nets.hip; Gibson 1998).  Not in the reference.  values (N, nx, ny, nz) float32, sample
  * (i, j, k) at flat index (i ny + j) nz + k, every axis 2 .. 1024 samples, one `iso` per call.
  *   Sides: a sample is inside iff value < iso, compared exactly, and the value is finite (value == iso, NaN, +-inf: outside).
